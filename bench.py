@@ -13,7 +13,10 @@ Multi-GPU (torchrun, one rank per GPU): weak scaling, each rank owns a
 1024-problem shard; the shared environment is broadcast from rank 0 over
 RCCL (the only collective besides the timing/iteration reductions).
 
-Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line on
+rank 0 (with --dump-outputs DIR it first writes what the last timed step
+computed).  --full adds the measurements that take runs of their own: the two
+CPU baselines (rank 0's host cores, before the process touches the GPU).
 """
 import argparse
 import json
@@ -273,6 +276,21 @@ def config_record(a, args, desc, B, N, D, O, opt, world, info, plan=None):
     }
 
 
+def dump_outputs(path, rank, world, alpha_t, traj_t, stats_t):
+    """What the last timed step's optimize_dev() left in the caller's buffers, as <name>.npy (at world > 1
+    <name>_rank<r>.npy, this rank's shard): alpha and traj (B, N, D) float32, stats (B, 8) float64 in the
+    order of _abi.STATS_FIELDS (seven int32 counters and the float32 final loss)."""
+    from irm_motion_planning_amd._abi import STATS_FIELDS
+    os.makedirs(path, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    st = stats_t.cpu().numpy()
+    stats = st.astype(np.float64)
+    k = STATS_FIELDS.index("final_loss")
+    stats[:, k] = st[:, k].copy().view(np.float32)
+    for name, arr in (("alpha", alpha_t.cpu().numpy()), ("traj", traj_t.cpu().numpy()), ("stats", stats)):
+        np.save(os.path.join(path, name + sfx + ".npy"), np.ascontiguousarray(arr))
+
+
 def launch_ranks(a):
     """`bench.py --gpus N` outside torchrun: start N ranks under torch.distributed.run as a CHILD
     process (nothing in this process has touched HIP) and relay rank 0's JSON line."""
@@ -374,7 +392,11 @@ def main():
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--faithful", action="store_true", help="reference control flow (early exits) instead of 200 fixed")
     ap.add_argument("--max-inner", type=int, default=200)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU baselines (scalar C oracle, batched fp32 numpy) for the cpu_baseline entry")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's alpha / traj / stats to DIR/<name>.npy")
     ap.add_argument("--operator-rank", type=int, default=0)
     ap.add_argument("--tb", type=int, default=0, help="trajectories per workgroup (0 = auto)")
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
@@ -400,12 +422,12 @@ def main():
     desc, B, N, D, O, opt = CONFIGS[a.config]
     args = make_args(a.config, a.faithful, a.max_inner)
     start, goal, obstacles = make_problem(a.config, world, rank)
-    # The CPU baselines run first, before this process touches the GPU — and, at world > 1, before the
+    # The CPU baselines (--full) run first, before this process touches the GPU — and, at world > 1, before the
     # process group exists: init_process_group("nccl", device_id=…) forms the RCCL communicator
     # eagerly, which initialises HIP on the device, and the batched baseline forks worker processes.
     # The other ranks wait for rank 0 in the rendezvous meanwhile.
     cpu = None
-    if rank == 0 and not a.no_cpu_baseline and not a.dry_run:
+    if rank == 0 and a.full and not a.no_cpu_baseline and not a.dry_run:
         cpu = cpu_baseline(a.config, args, start, goal, obstacles, world)
     if world > 1:
         tmo = rendezvous_timeout(world)
@@ -459,6 +481,8 @@ def main():
     elapsed = time.perf_counter() - t0
     kernel_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in evs]))
 
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rank, world, alpha_t, traj_t, stats_t)
     st = stats_t.cpu().numpy()
     iters_rank = float(st[:, 2].sum())  # grad_evals = executed inner iterations
     trials_rank = float(st[:, 4].sum())  # BLS line-search trials (one evaluation round each)
@@ -528,7 +552,7 @@ def main():
             "hbm_achieved_gbs": bytes_launch / (kernel_ms * 1e-3) / 1e9,
             "hbm_frac": bytes_launch / (kernel_ms * 1e-3) / 1e9 / PEAK_HBM_GBS,
         },
-        "cpu_baseline": cpu,  # rank 0's host cores, its own shard, every world size
+        "cpu_baseline": cpu,  # --full: rank 0's host cores, its own shard, every world size
         "iterations_per_step": iters_all,
     }
     if rank == 0:

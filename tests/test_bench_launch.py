@@ -89,12 +89,47 @@ def test_cpu_baseline_runs_before_process_group_init(monkeypatch):
     monkeypatch.setenv("WORLD_SIZE", "2")
     monkeypatch.setenv("RANK", "0")
     monkeypatch.setenv("LOCAL_RANK", "0")
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--config", "c3"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--config", "c3", "--full"])
     try:
         bench.main()
     except Stop:
         pass
     assert order == ["cpu_baseline", "init_process_group"], order
+    # a plain run (no --full) times no CPU baseline
+    del order[:]
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--config", "c3"])
+    try:
+        bench.main()
+    except Stop:
+        pass
+    assert order == ["init_process_group"], order
+
+
+def test_dump_outputs_writes_the_callers_arrays(tmp_path):
+    """--dump-outputs: alpha / traj as float32 and the stats records as float64 (counters exact, the final
+    loss the float32 the library wrote), one file per name, per-rank names at world > 1."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, REPO)
+    import bench
+    from irm_motion_planning_amd._abi import STATS_FIELDS
+    rs = np.random.default_rng(0)
+    alpha = rs.standard_normal((5, 7, 3)).astype(np.float32)
+    traj = rs.standard_normal((5, 7, 3)).astype(np.float32)
+    st = rs.integers(0, 1000, (5, 8)).astype(np.int32)
+    loss = rs.standard_normal(5).astype(np.float32)
+    st[:, STATS_FIELDS.index("final_loss")] = loss.view(np.int32)
+    bench.dump_outputs(str(tmp_path / "d"), 0, 1, torch.from_numpy(alpha), torch.from_numpy(traj), torch.from_numpy(st))
+    assert sorted(os.listdir(tmp_path / "d")) == ["alpha.npy", "stats.npy", "traj.npy"]
+    a, t, s = (np.load(tmp_path / "d" / (n + ".npy")) for n in ("alpha", "traj", "stats"))
+    assert a.dtype == t.dtype == np.float32 and s.dtype == np.float64
+    np.testing.assert_array_equal(a, alpha)
+    np.testing.assert_array_equal(t, traj)
+    np.testing.assert_array_equal(s[:, :7], st[:, :7])
+    np.testing.assert_array_equal(s[:, 7], loss.astype(np.float64))
+    bench.dump_outputs(str(tmp_path / "d2"), 1, 2, torch.from_numpy(alpha), torch.from_numpy(traj), torch.from_numpy(st))
+    assert sorted(os.listdir(tmp_path / "d2")) == ["alpha_rank1.npy", "stats_rank1.npy", "traj_rank1.npy"]
 
 
 import pytest  # noqa: E402

@@ -279,17 +279,48 @@ def test_main_cli_two_ranks_sharded(tmp_path):
 def test_bench_gpus_flag_runs_ranks():
     """`bench.py --gpus 2` outside torchrun launches two ranks itself and reports n_gpus = 2 with the
     whole job's iterations (the ranks share the box's one GPU, gloo collectives on host tensors); the
-    CPU baseline is kept on rank 0 at every world size."""
+    CPU baseline (`--full`) is kept on rank 0 at every world size."""
     import json
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-                        "--steps", "2", "--warmup", "1", "--max-inner", "20"], stdout=subprocess.PIPE,
+                        "--steps", "2", "--warmup", "1", "--max-inner", "20", "--full"], stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, env=env, timeout=300, cwd=repo)
     assert p.returncode == 0, p.stderr[-3000:]
     r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert r["n_gpus"] == 2 and r["config"]["global_batch"] == 2048
     assert r["iterations_per_step"] == 2 * 1024 * 20
     assert r["value"] > 0 and r["cpu_baseline"]["value"] > 0
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times exactly K steps, measures no CPU baseline and,
+    with --dump-outputs, writes what the last timed step left in the caller's buffers: bit for bit the
+    arrays the same library computes for the same (seeded) problems in this process."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    from irm_motion_planning_amd.context import Context
+    from irm_motion_planning_amd.params import params_from_args
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--max-inner", "20", "--dump-outputs", str(tmp_path / "out")], stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, env=env, timeout=300, cwd=repo)
+    assert p.returncode == 0, p.stderr[-3000:]
+    r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert r["steps"] == 2 and r["cpu_baseline"] is None
+    assert r["iterations_per_step"] == 1024 * 20
+    assert r["ms_per_step"] > 0 and abs(r["value"] * r["ms_per_step"] * 1e-3 - 1024 * 20) < 1e-6 * 1024 * 20
+    alpha, traj, stats = (np.load(tmp_path / "out" / (n + ".npy")) for n in ("alpha", "traj", "stats"))
+    assert alpha.dtype == traj.dtype == np.float32 and stats.dtype == np.float64
+    assert alpha.shape == traj.shape == (1024, 128, 3) and stats.shape == (1024, 8)
+    s, g, obs = bench.make_problem("c3", 1, 0)
+    a_here, t_here, st = Context(params_from_args(bench.make_args("c3", False, 20))).optimize(s, g, obs)
+    np.testing.assert_array_equal(alpha, a_here)
+    np.testing.assert_array_equal(traj, t_here)
+    np.testing.assert_array_equal(stats[:, 2], np.asarray(st["grad_evals"], np.float64))
+    np.testing.assert_array_equal(stats[:, 7].astype(np.float32), np.asarray(st["final_loss"], np.float32))

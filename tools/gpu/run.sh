@@ -25,7 +25,7 @@ show() {  # one summary line of a bench JSON file
 }
 bench_one() {  # bench_one <lib> <outfile> <cpu: yes|no> <config args...>
   local lib=$1 out=$2 cpu=$3; shift 3
-  local extra=""; [ "$cpu" = no ] && extra="--no-cpu-baseline"
+  local extra="--full"; [ "$cpu" = no ] && extra=""
   IRM_LIB=$(lib_of "$lib") timeout -k 10 300 python bench.py $extra --config "$@" > "$out" 2> "$out.err" || {
     echo "bench $* ($lib) failed"; tail -3 "$out.err"; exit 2; }
 }
