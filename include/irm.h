@@ -248,6 +248,33 @@ typedef struct irm_launch_plan {
 int irm_optimize_plan(const irm_ctx* ctx, int32_t batch, int32_t n_obstacles, int32_t record_series,
                       irm_launch_plan* out);
 
+/* Work queue: an opt-in scheduling mode of irm_optimize_batch(_dev) for the GD dual-loop and BLS
+ * flows, whose problems end after very different numbers of rounds.  The launch runs `groups`
+ * persistent workgroups; a workgroup slot whose problem has finished writes that problem's outputs,
+ * claims the next unsolved problem index from a device counter and loads it.  Results (α, trajectory,
+ * every irm_stats field) are bit-identical to the static launch.
+ *   groups = 0   off (the default: one workgroup per traj_per_block problems, as before)
+ *   groups > 0   that many persistent workgroups
+ *   groups = -1  auto: num_cus × the resident workgroups per CU of the kernel that runs, for the
+ *                flows where the queue measured faster (D = 3, N = 128, four problems
+ *                per 512-thread workgroup, BLS and GD dual loop); the static launch otherwise
+ * Other values, or a NULL ctx, return IRM_EINVAL.  The setting applies to every later
+ * irm_optimize_batch(_dev) on the context; contexts that never call this take IRM_WORK_QUEUE=off|auto|<n>
+ * from the environment (unset: off).  A launch keeps the static launch — and the query below returns
+ * 0 — when `groups` would cover every workgroup of the static launch (groups ≥ ⌈batch/traj_per_block⌉),
+ * when it records a series, and when it dispatches to a kernel without the queue (the GD single loop,
+ * k_optimize, the dense operator, two waypoints per lane, shapes other than D = 3 at N = 50 / 64 / 128 and
+ * D = 7 at N = 128).
+ * The 4-byte counter belongs to the context and is set by stream work ahead of the kernel
+ * (enqueue-only for _dev): at most one queued launch per context may be in flight.
+ * Additive symbols: IRM_ABI_VERSION stays 3 and no struct changes layout; no reference counterpart. */
+int irm_set_work_queue(irm_ctx* ctx, int32_t groups);
+/* The persistent workgroups that a launch of these arguments would run (the arguments of
+ * irm_optimize_plan), 0 for the static launch, a negative IRM_E* code on failure.  Filled in by the
+ * launch dispatch itself with nothing launched.  While the queue is active irm_optimize_plan reports
+ * this number as `grid` and a kernel label ending in ",QUEUE>". */
+int irm_work_queue_groups(const irm_ctx* ctx, int32_t batch, int32_t n_obstacles, int32_t record_series);
+
 /* Build id of the library: the first 16 hex digits of the SHA-256 over every file of
  * irm_motion_planning_amd/csrc and include/irm.h, the compile flags of every unit and the build
  * variant (build.py source_hash); "unknown" otherwise.

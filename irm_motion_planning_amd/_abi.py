@@ -175,6 +175,8 @@ PROTOTYPES = {
     "irm_optimize_plan": (
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(IrmLaunchPlan)]
     ),
+    "irm_set_work_queue": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
+    "irm_work_queue_groups": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "irm_build_id": (ctypes.c_char_p, []),
     "irm_debug_phase_profile": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
     "irm_debug_bls_trace_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),

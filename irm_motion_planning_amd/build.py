@@ -36,6 +36,7 @@ CFLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wall", "-Wno
           "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]
 FIX_SHAPES = [(3, 50), (3, 64), (3, 128), (3, 256), (7, 128), (7, 256)]  # IRM_FIX_SHAPES in irm_kernels_impl.hpp
 DENSE_SHAPES = [(7, 256)]  # the dense operator's k_lean (irm_kernels.hip launch_optimize)
+QUEUE_SHAPES = [(3, 50), (3, 64), (3, 128), (7, 128)]  # the work queue's k_lean (IRM_QUEUE_SHAPES in irm_kernels_impl.hpp)
 MAX_D = 8
 
 VARIANTS = {
@@ -105,6 +106,9 @@ def _units():
           for d, n in FIX_SHAPES]
     u += [(f"opt_dense{d}_{n}", "irm_opt_inst.hip", [f"-DIRM_INST_DENSE_D={d}", f"-DIRM_INST_DENSE_N={n}"])
           for d, n in DENSE_SHAPES]
+    # the work queue's kernels in units of their own: the opt_fix* units and their objects stay as they are
+    u += [(f"opt_fixq{d}_{n}", "irm_opt_inst.hip", [f"-DIRM_INST_FIXQ_D={d}", f"-DIRM_INST_FIXQ_N={n}"])
+          for d, n in QUEUE_SHAPES]
     return u
 
 

@@ -36,6 +36,20 @@ def default_jac(n_joints, jac_gaussian_mean=0.15, seed=0):
     return out.reshape(n_joints, n_joints)
 
 
+def parse_work_queue(groups):
+    """irm_set_work_queue's argument from "off" / "auto" / a count (int or decimal string)."""
+    if isinstance(groups, str):
+        word = groups.strip().lower()
+        if word == "off":
+            return 0
+        if word == "auto":
+            return -1
+        if not word.isdigit():
+            raise ValueError(f"work queue must be 'off', 'auto' or a workgroup count, got {groups!r}")
+        return int(word)
+    return int(groups)
+
+
 def default_params():
     p = IrmParams()
     load_library().irm_params_default(ctypes.byref(p))
@@ -84,6 +98,19 @@ class Context:
         d = {name: getattr(pl, name) for name, _ in IrmLaunchPlan._fields_}
         d["kernel"] = d["kernel"].decode()
         return d
+
+    def set_work_queue(self, groups):
+        """Work-queue scheduling of every later optimize() on this context (irm_set_work_queue):
+        "off" / 0, "auto", or the number of persistent workgroups.  Results do not depend on it."""
+        check(self.lib.irm_set_work_queue(self._h, parse_work_queue(groups)))
+
+    def work_queue_groups(self, batch, n_obstacles=0, series=False):
+        """Persistent workgroups of the launch optimize() runs for `batch` problems, 0 for the static
+        launch (irm_work_queue_groups: the library's own dispatch, nothing launched)."""
+        n = self.lib.irm_work_queue_groups(self._h, int(batch), int(n_obstacles), int(bool(series)))
+        if n < 0:
+            check(n)
+        return int(n)
 
     def kernel_matrices(self):
         N, D = self.N, self.D

@@ -307,6 +307,7 @@ struct irm_ctx {
     int prof_blocks = 0, prof_cap = 0;
     float* d_trace = nullptr;  // BLS line-search log of problem 0 (irm_debug_bls_trace)
     int trace_cap = 0;
+    int32_t* d_queue = nullptr;  // the work queue's problem counter (kp.queue; the request is kp.queue_groups)
 };
 
 namespace {
@@ -882,7 +883,18 @@ int irm_ctx_create(irm_ctx** out, const irm_params* p) {
         kp.lean_nohelp = (nh && nh[0] == '1') ? 1 : 0;
         const char* tp = getenv("IRM_TRACE_PROBLEM");
         kp.trace_b = tp ? atoi(tp) : 0;
+        // IRM_WORK_QUEUE=off|auto|<n>: the context's work-queue request until irm_set_work_queue is called
+        const char* wq = getenv("IRM_WORK_QUEUE");
+        kp.queue_groups = 0;
+        if (wq && !strcmp(wq, "auto")) kp.queue_groups = -1;
+        else if (wq && strcmp(wq, "off")) kp.queue_groups = std::max(0, atoi(wq));
     }
+    kp.num_cus = c->num_cus;
+    if (hipMalloc(&c->d_queue, 256) != hipSuccess) {
+        irm_ctx_destroy(c);
+        return fail(IRM_ENOMEM, "hipMalloc of the work-queue counter failed");
+    }
+    kp.queue = c->d_queue;
     c->max_series = p->max_series > 0 ? p->max_series : 1 + p->max_outer_iteration * p->max_inner_iteration;
     kp.max_series = c->max_series;
 
@@ -914,6 +926,7 @@ void irm_ctx_destroy(irm_ctx* c) {
     if (c->d_io) (void)hipFree(c->d_io);
     if (c->d_prof) (void)hipFree(c->d_prof);
     if (c->d_trace) (void)hipFree(c->d_trace);
+    if (c->d_queue) (void)hipFree(c->d_queue);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1246,6 +1259,30 @@ int irm_optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int3
     out->lam16 = c->lam16;
     out->lam24 = c->lam24;
     return IRM_OK;
+}
+
+int irm_set_work_queue(irm_ctx* c, int32_t groups) {
+    if (!c) return fail(IRM_EINVAL, "irm_set_work_queue: null context");
+    if (groups < -1) return fail(IRM_EINVAL, "irm_set_work_queue: groups=%d (0 off, > 0 workgroups, -1 auto)", groups);
+    c->kp.queue_groups = groups;
+    return IRM_OK;
+}
+
+int irm_work_queue_groups(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series) {
+    if (!c) return fail(IRM_EINVAL, "irm_work_queue_groups: null context");
+    if (batch < 0) return fail(IRM_EINVAL, "irm_work_queue_groups: negative batch");
+    if (check_obs(n_obstacles)) return IRM_EINVAL;
+    if (batch == 0 || c->kp.queue_groups == 0) return 0;
+    if (set_device(c)) return IRM_EDEVICE;
+    KParams kp = c->kp;
+    kp.B = batch;
+    kp.O = n_obstacles;
+    kp.record_series = (c->kp.record_series || record_series) ? 1 : 0;
+    if (choose_shape(c, batch, true, kp, nullptr) <= 0) return fail(IRM_EINVAL, "no workgroup shape fits LDS");
+    irm::LaunchDesc d{};
+    d.describe_only = true;
+    HIP_TRY(irm::launch_optimize(kp, nullptr, &d));  // the dispatch fills d and launches nothing
+    return d.queue_groups;
 }
 
 const char* irm_build_id(void) {

@@ -99,6 +99,12 @@ struct KParams {
     // diagnostics: BLS line-search log of problem 0 (irm_debug_bls_trace), kTraceW floats per trial
     float* trace;
     int32_t trace_cap;
+    // work queue (irm_set_work_queue): the request of this launch — 0 static launch, > 0 that many persistent
+    // workgroups, -1 auto (num_cus × the resident workgroups per CU of the instantiation) — and the
+    // context's problem counter, which the dispatch sets to grid·TB on the launch's stream
+    int32_t queue_groups;
+    int32_t num_cus;
+    int32_t* queue;
 };
 
 constexpr int kTraceW = 10;  // outer, inner, trial, lr, new_loss, required_loss, accepted, loss, ‖g‖, alpha_norm
@@ -322,6 +328,7 @@ struct LaunchDesc {
     int wpl;           // waypoints per lane
     int threads, grid, lds_bytes, traj_per_block;
     int rank_z, rank_dir, rank_g;  // operator rank of the residual projection, the waypoint direction, G
+    int queue_groups;  // persistent workgroups of a work-queue launch (0: the static launch)
 };
 
 // launchers (return hipError_t)

@@ -2029,7 +2029,7 @@ __device__ __forceinline__ void ered_store_wpl(const bool (&live)[WPL], const fl
 enum LeanFlow : int { LF_GD1 = 0, LF_GD2 = 1, LF_BLS = 2 };
 // Per-trajectory phase (LF_GD2 / LF_BLS): a GD step or BLS trial this round, the end of an inner
 // loop (α's exact trajectory, constraintsFulfilled, λ escalation), done.
-enum LeanPhase : int { LP_STEP = 0, LP_RESYNC = 1, LP_DONE = 2 };
+enum LeanPhase : int { LP_STEP = 0, LP_RESYNC = 1, LP_DONE = 2, LP_LOAD = 3 };
 // BLS line-search helpers (k_lean): when one trajectory of a workgroup is left, the first done slot
 // evaluates its next trial (lr·β₋) in the same round.  D ≤ 3, one waypoint per lane, N ≤ 128 in
 // 512-thread workgroups (or N ≤ 64): where the exchange regions fit the LDS at full occupancy.
@@ -2041,9 +2041,18 @@ constexpr bool lean_help() {
 // FULL: the launch has exactly MAXT threads, so the stage-2 tiles per wave are known exactly
 // (otherwise kS2T(MAXT) bounds them for smaller launches): C7's 256-thread variant then holds 4
 // tiles of operator fragments instead of 8 (32 VGPRs) and does not spill.
-template <class S, int MAXT, int WPL, bool FULL = false, int FLOW = LF_GD1>
+//
+// QUE: the work queue (LF_GD2 / LF_BLS, one waypoint per lane).  The launch runs a fixed number of
+// workgroups; a slot whose problem has finished writes its outputs, takes the next problem index from
+// the device counter P.queue (the host sets it to grid·TB) and loads it in the next round (LP_LOAD): that
+// round is a resync round of the slot — α0 into its X columns, the exact trajectory, the evaluation with
+// the first outer iteration's λ — followed by round 0's decision.  An index ≥ B leaves the slot done for
+// good.  No workgroup waits on another: a workgroup leaves when its flag word is empty.
+template <class S, int MAXT, int WPL, bool FULL = false, int FLOW = LF_GD1, bool QUE = false>
 __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lean(KParams P) {
     constexpr bool GD1 = FLOW == LF_GD1, BLS = FLOW == LF_BLS;
+    static_assert(!QUE || (FLOW != LF_GD1 && WPL == 1 && FULL && !S::kDense),
+                  "the work queue serves the dual-loop / BLS flows of the fixed shapes, one waypoint per lane");
     constexpr int D = S::D;
     constexpr int S1Q = kS1Q(MAXT);
     // stage-2 tiles per wave: all of this shape's tiles over the workgroup's waves (N = 256: 4)
@@ -2090,8 +2099,8 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     bool wl[WPL];  // vl[j] where the trajectory is known to be valid
 #pragma unroll
     for (int j = 0; j < WPL; ++j) wl[j] = kAllLive || nn[j] < N;
-    const size_t b = (size_t)(tb0 + (tvalid ? t : 0));
-    const bool rec = !GD1 && P.record_series && P.series;
+    size_t b = (size_t)(tb0 + (tvalid ? t : 0));  // (QUE: the slot's current problem)
+    const bool rec = !GD1 && !QUE && P.record_series && P.series;
     Prof prof;
     if (tid == 0) prof.init();
 
@@ -3350,11 +3359,13 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         }
     };
     bool adopt = false;  // t*: the helper's trial was accepted — take its α, T, V at the next round's start
+    bool qpend = false;  // QUE: this slot took a queue index at the end of the previous round (wave-uniform)
     // BLS: this trajectory's trial scalars for the trial stages (lr of its next trial, in a line search)
     auto ts_write = [&]() {
         if (n0 == 0 && lane == 0) {
             TS[t * kTsW + 0] = lr;
             TS[t * kTsW + 2] = phase == LP_STEP ? 1.f : 0.f;
+            if constexpr (QUE) TS[t * kTsW + 3] = __int_as_float((int)b);  // the slot's problem, for a helper
         }
     };
     int n_rounds = 0, n_hm = 0;  // diagnostics (trace_b bit 29): kernel rounds / helper rounds until this trajectory ended
@@ -3473,6 +3484,18 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         const bool dirr = GD1 || ((fl >> 28) & 1u);  // some trajectory needs a direction this round
         const bool rsy = !GD1 && ((fl >> 29) & 1u);  // some trajectory ends an inner loop this round
         if (tid == 0) fw[par ^ 1] = 0u;
+        if constexpr (QUE) {
+            // the index this slot's first wave took at the end of the previous round (its record's spare word):
+            // a problem to load this round, or past the batch — the slot stays done
+            if (qpend) {
+                const int nx = __builtin_amdgcn_readfirstlane(__float_as_int(red[(t * WPTL) * 8 + 6]));
+                qpend = false;
+                if (nx < P.B) {
+                    b = (size_t)nx;
+                    phase = LP_LOAD;
+                }
+            }
+        }
         bool hm = false, helper = false;  // helper round (block-uniform) / this wave helps
         int ts = 0, hs = 0;               // t*, the helper slot
         float h_lr0 = 0.f, h_lr = 0.f, h_ljl = 0.f, h_lsg = 0.f, h_loss = 0.f, h_gn = 1.f, h_an = 0.f;
@@ -3528,7 +3551,8 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             }
             if (helper) {  // wave-uniform: t*'s state and scalars (its own trajectory is done and written out)
                 if constexpr (!kSSLazy) ss_read(ts);
-                const size_t bs = (size_t)(tb0 + ts);
+                // t*'s problem: its place in the launch, or (QUE) the index its slot claimed
+                const size_t bs = QUE ? (size_t)__float_as_int(TS[ts * kTsW + 3]) : (size_t)(tb0 + ts);
 #pragma unroll
                 for (int k = 0; k < D; ++k) tg[0][k] = (nn[0] == N - 1) ? P.goal[bs * D + k] : P.start[bs * D + k];
                 vl[0] = wl[0];
@@ -3636,7 +3660,57 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         }
         // ------------------------------------------------ end of an inner loop: α's exact trajectory
         if (rsy) {  // block-uniform
-            const bool rs = phase == LP_RESYNC;  // wave-uniform
+            const bool rs = phase == LP_RESYNC || (QUE && phase == LP_LOAD);  // wave-uniform
+            if constexpr (QUE) {
+                if (phase == LP_LOAD) {
+                    // the claimed problem b into this slot: everything the prologue sets per trajectory.  The
+                    // slot's registers may have served as a helper (vl, obs, tg, oreg), its LDS rows and words
+                    // hold the finished problem's
+                    vl[0] = nn[0] < N;
+#pragma unroll
+                    for (int k = 0; k < D; ++k) tg[0][k] = (nn[0] == N - 1) ? P.goal[b * D + k] : P.start[b * D + k];
+                    if (P.alpha0) {
+#pragma unroll
+                        for (int k = 0; k < D; ++k) al[0][k] = vl[0] ? P.alpha0[(b * N + nn[0]) * D + k] : 0.f;
+                    } else {  // stage_alpha's α0, the same operations in the same order
+                        const float un = vl[0] ? P.uvec[nn[0]] : 0.f, wn = vl[0] ? P.wvec[nn[0]] : 0.f;
+#pragma unroll
+                        for (int k = 0; k < D; ++k) {
+                            float sj = 0.f, gj = 0.f;
+#pragma unroll
+                            for (int e2 = 0; e2 < D; ++e2) {
+                                sj += P.start[b * D + e2] * P.Jinv[e2 * D + k];
+                                gj += P.goal[b * D + e2] * P.Jinv[e2 * D + k];
+                            }
+                            al[0][k] = vl[0] ? un * sj + wn * gj : 0.f;
+                        }
+                    }
+                    if constexpr (BLS) {  // the α rows of the trial stages
+                        if (vl[0]) {
+#pragma unroll
+                            for (int k = 0; k < D; ++k) Ab[(t * D + k) * lde + swz(nn[0], t * D + k)] = al[0][k];
+                        }
+                    }
+                    obs = obsL + (P.obs_stride ? t * obs_pitch(P.O) : 0);
+                    if (P.obs_stride) {  // the problem's own obstacle table (stage_obstacles' layout)
+                        const int pitch = obs_pitch(P.O);
+                        for (int r = li; r < pitch; r += NWL) {
+                            const int o = 2 * (r >> 2) + (r & 1), coord = (r >> 1) & 1;
+                            obsL[t * pitch + r] = o < P.O ? P.obstacles[b * P.obs_stride + 2 * o + coord] : 1.0e20f;
+                        }
+                    }
+                    lsg = P.lsg0;
+                    ljl = P.ljl0;
+                    lr = BLS ? P.bls_lr0 : P.gd_lr[0];
+                    cfac = P.gd_c[0];
+                    gnorm = 1.f;
+                    anorm = 0.f;
+                    outer = inner = trial = 0;
+                    needs_dir = xdense = adopt = false;
+                    n_rounds = n_hm = 0;
+                    st = irm_stats{};
+                }
+            }
             if (rs) {
 #pragma unroll
                 for (int j = 0; j < WPL; ++j) {
@@ -3650,6 +3724,12 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                 }
             }
             __syncthreads();
+            if constexpr (QUE && OREG) {  // (the register copy of the loaded problem's table)
+                if (phase == LP_LOAD && P.obs_stride && obs_reg) {
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) oreg[i] = reinterpret_cast<const f32x4*>(obs)[i];
+                }
+            }
             if (rs) {
 #pragma unroll
                 for (int j = 0; j < WPL; ++j) {
@@ -3793,6 +3873,18 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                     st.inner_iterations++;
                     if (inner >= P.max_inner) done = true;
                     else more = true;
+                }
+            } else if (QUE && phase == LP_LOAD) {
+                // round 0 of the loaded problem (optimizer_GD.py:93 / :210: the loss at α0), as after the prologue
+                loss = f.nl;
+                if constexpr (!BLS) st.cost_evals = 1;
+                bool te = P.max_inner <= 0;
+                if constexpr (BLS) te = te || P.max_outer <= 0;  // α0 is returned (optimizer_BLS.py:184-186)
+                if (te) {
+                    to_end = true;
+                } else {
+                    phase = LP_STEP;
+                    more = true;
                 }
             } else if (rs) {
                 // constraintsFulfilled(α) (trajectory.py:129-137, robot.py:90-113) on α's exact
@@ -3976,6 +4068,20 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                         write_out();
                     }
                 }
+                if constexpr (QUE) {
+                    if (phase == LP_DONE) {  // (only valid slots get here)
+                        if constexpr (!kHelp) write_out();
+                        // the next problem: one lane of the slot's first wave takes an index; the slot's waves
+                        // read it after the round-end barrier.  A problem to load keeps the slot's wave bits
+                        // set and asks for a resync round (its carrier)
+                        if (n0 == 0 && lane == 0) {
+                            const int nx = atomicAdd(P.queue, 1);
+                            red[wave * 8 + 6] = __int_as_float(nx);
+                            if (nx < P.B) atomicOr(&fw[par ^ 1], (((1u << WPTL) - 1u) << wave) | 1u << 29);
+                        }
+                        qpend = true;
+                    }
+                }
                 if (lane == 0 && phase != LP_DONE)
                     atomicOr(&fw[par ^ 1], (1u << wave) | (needs_dir ? 1u << 28 : 0u) |
                                                (phase == LP_RESYNC ? 1u << 29 : 0u) | (phase == LP_STEP ? 1u << 30 : 0u) |
@@ -4021,7 +4127,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     }
     // (LF_GD2 / LF_BLS: every trajectory ended through LP_RESYNC — q, v are α's exact trajectory;
     // kHelp: written when the trajectory finished)
-    if (!kHelp && tvalid) write_out();
+    if (!kHelp && !QUE && tvalid) write_out();
     if (tid == 0) prof.flush(P.prof);
 }
 
@@ -4235,6 +4341,82 @@ hipError_t launch_lean_flow(const KParams& p, int flow, int grid, hipStream_t s,
     }
 }
 
+// The work queue's instantiations k_lean<Sh, 256 / 512, 1, FULL, GD2 / BLS, QUE> (units of their own,
+// irm_opt_inst.hip IRM_INST_FIXQ_*): one waypoint per lane.
+template <class Sh>
+constexpr bool lean_queue_shape() {
+    if constexpr (Sh::kNW > 0 && !Sh::kDense && !Sh::kVariants)  // (a fixed shape: N is a constant)
+        return (Sh::D == 3 && (Sh::N == 50 || Sh::N == 64 || Sh::N == 128)) || (Sh::D == 7 && Sh::N == 128);
+    else
+        return false;
+}
+// Auto (irm_set_work_queue(ctx, -1)) selects the queue only where it measured faster than the static launch
+// by more than the spread of repeated launches (profiles/work_queue_ab.json): the C3 shape's
+// four-trajectory 512-thread workgroups, BLS −16 %, GD dual loop −7.5 % at B = 8,192.  (7-DoF N = 128 won
+// 7 % with two workgroups per CU and lost 35 % with one; it and the unmeasured shapes stay explicit.)
+constexpr bool lean_queue_auto(int D, int N, int threads, int flow) {
+    return D == 3 && N == 128 && threads == 512 && (flow == LF_BLS || flow == LF_GD2);
+}
+// Serves a launch whose context asks for the queue (p.queue_groups != 0) with G < `grid` persistent
+// workgroups: sets the problem counter to G·TB on the stream, then launches.  *served = false leaves the
+// launch to the static dispatch (the request covers every workgroup, auto does not select this flow).
+template <class Sh>
+hipError_t launch_lean_queue(const KParams& p, int flow, int grid, hipStream_t s, LaunchDesc* desc, bool* served);
+
+template <class Sh, int TT, int FLOW>
+hipError_t launch_lean_queue_flow(const KParams& p, int grid, hipStream_t s, LaunchDesc* desc, bool* served) {
+    auto kernel = k_lean<Sh, TT, 1, true, FLOW, true>;
+    const size_t lds = lean_lds(p, lean_help<Sh, TT, 1, true, FLOW>(), FLOW == LF_BLS, false);
+    int G = p.queue_groups;
+    if (G < 0) {  // auto: every CU full of resident workgroups, as the runtime counts them for this LDS request
+        if (!lean_queue_auto(Sh::D, Sh::N, TT, FLOW)) return hipSuccess;
+        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        int per_cu = 0;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, TT, lds);
+        if (e != hipSuccess) return e;
+        G = p.num_cus * per_cu;
+    }
+    if (G <= 0 || G >= grid || !p.queue) return hipSuccess;
+    *served = true;
+    if (desc) {
+        char sn[48];
+        shape_name<Sh>(sn, sizeof(sn));
+        snprintf(desc->kernel, sizeof(desc->kernel), "k_lean<%s,%d,1,FULL,%s,QUEUE>", sn, TT, flow_name(FLOW));
+        desc->lean = 1;
+        desc->flow = FLOW;
+        desc->wpl = 1;
+        desc->rank_z = desc->rank_dir = 16;
+        desc->rank_g = 24;
+        desc->queue_groups = G;
+    }
+    if (!desc || !desc->describe_only) {
+        const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)p.queue, G * p.TB, 1, s);
+        if (e != hipSuccess) return e;
+    }
+    return run_optimizer(desc, kernel, G, p.BT, lds, s, p);
+}
+
+template <class Sh>
+hipError_t launch_lean_queue(const KParams& p, int flow, int grid, hipStream_t s, LaunchDesc* desc, bool* served) {
+    *served = false;
+    if (p.BT == 512) {
+        if (flow == LF_GD2) return launch_lean_queue_flow<Sh, 512, LF_GD2>(p, grid, s, desc, served);
+        if (flow == LF_BLS) return launch_lean_queue_flow<Sh, 512, LF_BLS>(p, grid, s, desc, served);
+    } else if (p.BT == 256) {
+        if (flow == LF_GD2) return launch_lean_queue_flow<Sh, 256, LF_GD2>(p, grid, s, desc, served);
+        if (flow == LF_BLS) return launch_lean_queue_flow<Sh, 256, LF_BLS>(p, grid, s, desc, served);
+    }
+    return hipSuccess;
+}
+// (the shapes of lean_queue_shape; build.py QUEUE_SHAPES.  Declared here so that the dispatch units call
+// the queue units' instantiations instead of compiling their own)
+#define IRM_QUEUE_SHAPES(X) X(3, 50) X(3, 64) X(3, 128) X(7, 128)
+#define IRM_EXTERN_FIXQ(D_, N_)                                                                                   \
+    extern template hipError_t launch_lean_queue<FixShape<D_, N_, 32>>(const KParams&, int, int, hipStream_t, \
+                                                                       LaunchDesc*, bool*);
+IRM_QUEUE_SHAPES(IRM_EXTERN_FIXQ)
+
 template <class Sh>
 hipError_t launch_optimize_shape(const KParams& p, hipStream_t s, LaunchDesc* desc) {
     const int grid = (p.B + p.TB - 1) / p.TB;
@@ -4255,8 +4437,17 @@ hipError_t launch_optimize_shape(const KParams& p, hipStream_t s, LaunchDesc* de
         if constexpr (!Sh::kVariants && TT <= 512) {  // the lean kernel (F operators register-resident:
             // one stage-1 unit per wave; workgroups are padded to TT threads by choose_shape)
             const bool help = flow == LF_BLS && lean_help<Sh, TT, 1, true, LF_BLS>();
-            if (flow >= 0 && p.BT == TT && lean_fits(p, help, flow == LF_BLS))
+            if (flow >= 0 && p.BT == TT && lean_fits(p, help, flow == LF_BLS)) {
+                if constexpr (lean_queue_shape<Sh>()) {
+                    // the work queue, where the context asks for it (series launches keep the static launch)
+                    if (p.queue_groups != 0 && flow != LF_GD1 && !p.record_series) {
+                        bool served = false;
+                        const hipError_t e = launch_lean_queue<Sh>(p, flow, grid, s, desc, &served);
+                        if (served || e != hipSuccess) return e;
+                    }
+                }
                 return launch_lean_flow<Sh, TT, 1, true>(p, flow, grid, s, desc);
+            }
         }
         if constexpr (!Sh::kVariants && TT == 1024) {
             if constexpr (Sh::kNW == 256 && Sh::D * 3 <= kCols) {  // ≥ 3 trajectories fit the MFMA columns

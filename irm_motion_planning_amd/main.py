@@ -7,7 +7,7 @@ the stdout lines ("setup object, jit-compile took", "took X ms",
 files trajectory_result.txt / trajectory_series.txt (np.savetxt defaults).
 
 Additive flags (no reference counterpart): --batch-size, --seed,
---operator-rank, --device, --whole-robot-cost.
+--operator-rank, --device, --whole-robot-cost, --work-queue.
 """
 import argparse
 import os
@@ -22,6 +22,16 @@ from .optimizer_GD import GradientDescentOptimizer
 
 def _bool(x):
     return str(x).lower() == "true"
+
+
+def _work_queue(x):
+    """--work-queue: off, auto, or a number of persistent workgroups (> 0)."""
+    word = str(x).strip().lower()
+    if word in ("off", "auto"):
+        return word
+    if not word.isdigit() or int(word) <= 0:
+        raise argparse.ArgumentTypeError(f"expected off, auto or a positive workgroup count, got {x!r}")
+    return int(word)
 
 
 def build_parser():
@@ -109,6 +119,10 @@ def build_parser():
     parser.add_argument('--whole-robot-cost', type=_bool, default=False,
                         help="Obstacle cost summed over every joint position instead of the end effector only "
                              "(blog 'Complete Robot Obstacle Avoidance'; default: False)")
+    parser.add_argument('--work-queue', type=_work_queue, default='off', metavar='{off,auto,N}',
+                        help="Batched path: run N persistent workgroups (auto: as many as the GPU holds) whose "
+                             "finished slots claim the next problem, instead of one workgroup per fixed group of "
+                             "problems; same results (default: off)")
     return parser
 
 
@@ -138,6 +152,13 @@ def run_batch(optimizer, args):
         obs, start, goal = distributed.broadcast_environment(env.obstacles, start, goal, dev)
         env.obstacles = obs
         lo, hi = distributed.shard(B, world, rank)
+    wq = getattr(args, "work_queue", "off")
+    if wq != "off":  # this process's launch (single GPU, or this rank's shard)
+        ctx = optimizer.context
+        ctx.set_work_queue(wq)
+        n_obs = int(np.asarray(env.obstacles).reshape(-1, 2).shape[0])
+        if ctx.work_queue_groups(hi - lo, n_obs, args.extended_vis) == 0 and rank == 0:
+            print("work queue", wq, "ignored: this launch runs one workgroup per group of problems")
     runtimes = []
     res = None
     for _ in range(args.n_measurements):

@@ -1,0 +1,103 @@
+"""The work queue's host surface without a GPU: the two C-ABI functions are declared, exported and bound
+with the declared argument types, the CLI flag parses, and the queue's compilation units are part of
+the build (so the build id covers them)."""
+import ctypes
+import os
+import re
+
+import pytest
+
+from conftest import REPO
+
+HEADER = os.path.join(REPO, "include", "irm.h")
+C_TYPES = {"irm_ctx*": ctypes.c_void_p, "const irm_ctx*": ctypes.c_void_p, "int32_t": ctypes.c_int32, "int": ctypes.c_int}
+
+
+def _declaration(name):
+    """(return type, [argument types]) of `name` as include/irm.h declares it."""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    m = re.search(r"^\s*(\w[\w\s\*]*?)\s*\b%s\s*\(([^)]*)\)\s*;" % name, src, re.M)
+    assert m, f"{name} is not declared in include/irm.h"
+    args = []
+    for a in m.group(2).split(","):
+        words = a.replace("*", "* ").split()
+        args.append(" ".join(words[:-1]).replace(" *", "*"))  # drop the parameter's name
+    return m.group(1).strip(), args
+
+
+@pytest.mark.parametrize("name", ["irm_set_work_queue", "irm_work_queue_groups"])
+def test_declared_exported_and_bound(name):
+    from irm_motion_planning_amd._abi import PROTOTYPES, load_library
+    ret, args = _declaration(name)
+    assert name in PROTOTYPES
+    res, argtypes = PROTOTYPES[name]
+    assert res is C_TYPES[ret]
+    assert argtypes == [C_TYPES[a] for a in args], (args, argtypes)
+    fn = getattr(load_library(), name)
+    assert fn.argtypes == argtypes and fn.restype is res
+
+
+def test_declared_signatures():
+    assert _declaration("irm_set_work_queue") == ("int", ["irm_ctx*", "int32_t"])
+    assert _declaration("irm_work_queue_groups") == ("int", ["const irm_ctx*", "int32_t", "int32_t", "int32_t"])
+
+
+def test_abi_version_unchanged():
+    from irm_motion_planning_amd import _abi
+    assert _abi.IRM_ABI_VERSION == 3
+    assert re.search(r"#define IRM_ABI_VERSION 3\b", open(HEADER).read())
+
+
+def test_null_context_is_einval():
+    from irm_motion_planning_amd._abi import load_library
+    lib = load_library()
+    IRM_EINVAL = -22
+    assert lib.irm_set_work_queue(None, 1) == IRM_EINVAL
+    assert b"irm_set_work_queue" in lib.irm_last_error()
+    assert lib.irm_work_queue_groups(None, 8, 0, 0) == IRM_EINVAL
+
+
+def test_cli_flag():
+    from irm_motion_planning_amd import main
+    assert main.parse_args([]).work_queue == "off"
+    assert main.parse_args(["--work-queue", "off"]).work_queue == "off"
+    assert main.parse_args(["--work-queue", "auto"]).work_queue == "auto"
+    assert main.parse_args(["--work-queue", "7"]).work_queue == 7
+    for bad in ("-3", "x", "0", "1.5"):
+        with pytest.raises(SystemExit):
+            main.parse_args(["--work-queue", bad])
+
+
+def test_context_argument_words():
+    from irm_motion_planning_amd.context import parse_work_queue
+    assert parse_work_queue("off") == 0 and parse_work_queue("auto") == -1
+    assert parse_work_queue("12") == 12 and parse_work_queue(5) == 5 and parse_work_queue(-2) == -2
+    with pytest.raises(ValueError):
+        parse_work_queue("fast")
+
+
+def test_queue_units_are_built():
+    """One unit per queue shape, each compiled from irm_opt_inst.hip with its IRM_INST_FIXQ_* pair; the
+    existing opt_fix* units keep their flags."""
+    from irm_motion_planning_amd import build
+    units = {u[0]: u for u in build.units()}
+    assert build.QUEUE_SHAPES, "no queue shapes"
+    for d, n in build.QUEUE_SHAPES:
+        _, src, flags = units[f"opt_fixq{d}_{n}"]
+        assert src == "irm_opt_inst.hip"
+        assert flags == [f"-DIRM_INST_FIXQ_D={d}", f"-DIRM_INST_FIXQ_N={n}"]
+        assert (d, n) in build.FIX_SHAPES  # the dispatch unit that calls it
+        assert not any("FIXQ" in f for f in units[f"opt_fix{d}_{n}"][2])
+    # the shape list of the kernels' header and the build's agree
+    hpp = open(os.path.join(build.CSRC, "irm_kernels_impl.hpp")).read()
+    m = re.search(r"#define IRM_QUEUE_SHAPES\(X\)(.*)", hpp)
+    assert m and sorted(map(tuple, (map(int, p) for p in re.findall(r"X\((\d+),\s*(\d+)\)", m.group(1))))) == \
+        sorted(build.QUEUE_SHAPES)
+    # and the build id moves with them: a unit list without the queue units hashes differently
+    full = build.source_hash()
+    orig = build._units
+    try:
+        build._units = lambda: [u for u in orig() if not u[0].startswith("opt_fixq")]
+        assert build.source_hash() != full
+    finally:
+        build._units = orig
