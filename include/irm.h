@@ -275,6 +275,46 @@ int irm_set_work_queue(irm_ctx* ctx, int32_t groups);
  * this number as `grid` and a kernel label ending in ",QUEUE>". */
 int irm_work_queue_groups(const irm_ctx* ctx, int32_t batch, int32_t n_obstacles, int32_t record_series);
 
+/* Evaluation at arbitrary times (eval_any): the trajectory is the RKHS function q(t) = K(·, t)·α·J,
+ * v(t) = dK(·, t)·α·J for any t (DevBlog-Theme/blog-post.html:119-131; Trajectory.eval_any,
+ * trajectory.py:68-70).  A context holds one grid of M evaluation times and its query matrices Kq, dKq
+ * (M×N): row i is the evaluation time t_eval[i], column j the support time t[j], and the entry is
+ * kernel_f(t[j], t_eval[i]) in the arithmetic of K / dK (fp32 d = t[j] − t_eval[i]), so t_eval = t
+ * gives K and dK themselves.  (The reference's eval_any hands create_kernel_matrix its arguments in the
+ * other order and is never called; this is what its km / dkm and the blog's formula define.)
+ * Times need not be sorted nor lie in [0, 1]; a non-finite time, or M outside [1, IRM_MAX_EVAL_TIMES],
+ * is IRM_EINVAL.  Additive symbols: IRM_ABI_VERSION stays 3 and no struct changes layout. */
+#define IRM_MAX_EVAL_TIMES 4096
+/* Kq, dKq (M×N, row = evaluation time) for N support times linspace(0,1,N) as Trajectory.__init__ builds
+ * them; outputs nullable.  Needs no context and no device. */
+int irm_query_matrices(int32_t n_timesteps, float rbf_variance, const float* t_eval, int32_t M, float* kq, float* dkq);
+/* Builds and uploads Kq / dKq for t_eval (M); replaces the previous grid. */
+int irm_set_eval_times(irm_ctx* ctx, const float* t_eval, int32_t M);
+/* The M currently set (0 if none; a negative IRM_E* code on failure); t_out (nullable) receives the times. */
+int32_t irm_eval_times(const irm_ctx* ctx, float* t_out);
+/* blog :121-131 / trajectory.py:68-70: out (B×M×D) = Kq·α·J (which 0) or dKq·α·J (which 1), with
+ * irm_evaluate's arithmetic (fp64 sum of the exact products over m = 0..N−1, one rounding, then ·J the
+ * same way).  IRM_EINVAL before any irm_set_eval_times; batch = 0 is a no-op. */
+int irm_eval_any(irm_ctx* ctx, const float* alpha, int32_t batch, int32_t which, float* out);
+/* Limits and obstacle clearance of B trajectories on the M evaluation times (one record per trajectory).
+ * The start/goal terms are not part of it: they live on the support grid's end points (irm_constraints). */
+typedef struct irm_dense_report {
+    float max_cost, avg_cost;          /* obstacle cost over the M times: end effector, or whole robot if the context says so */
+    int32_t argmax_cost;               /* first index into t_eval attaining max_cost */
+    float max_position, min_position;  /* over times and joints, as trajectory.max()/min() in constraintsFulfilledVerbose */
+    float max_abs_velocity;
+    int32_t argmax_abs_velocity;       /* first index into t_eval */
+    int32_t position_ok, velocity_ok;  /* robot.py:104-113 applied to the M samples */
+    int32_t pad_;
+} irm_dense_report;
+/* obstacles: O×2 (obstacle_stride 0) or one table per trajectory, as irm_optimize_batch takes them.
+ * cost_out: B×M per-sample obstacle cost, nullable. */
+int irm_dense_check(irm_ctx* ctx, const float* alpha, const float* obstacles, int32_t n_obstacles, int32_t obstacle_stride,
+                    int32_t batch, irm_dense_report* report_out, float* cost_out);
+/* Same, device pointers, enqueue-only on `stream` (hipStream_t). */
+int irm_dense_check_dev(irm_ctx* ctx, const float* alpha_dev, const float* obstacles_dev, int32_t n_obstacles,
+                        int32_t obstacle_stride, int32_t batch, irm_dense_report* report_dev, float* cost_dev, void* stream);
+
 /* Build id of the library: the first 16 hex digits of the SHA-256 over every file of
  * irm_motion_planning_amd/csrc and include/irm.h, the compile flags of every unit and the build
  * variant (build.py source_hash); "unknown" otherwise.

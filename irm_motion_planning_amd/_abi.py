@@ -16,6 +16,7 @@ IRM_MAX_JOINTS = 8
 IRM_MAX_TIMESTEPS = 512
 IRM_MAX_OBSTACLES = 64
 IRM_MAX_LR = 32
+IRM_MAX_EVAL_TIMES = 4096
 
 IRM_OPT_GD = 0
 IRM_OPT_BLS = 1
@@ -136,6 +137,24 @@ class IrmBatchDev(ctypes.Structure):
     ]
 
 
+class IrmDenseReport(ctypes.Structure):
+    _fields_ = [
+        ("max_cost", ctypes.c_float),
+        ("avg_cost", ctypes.c_float),
+        ("argmax_cost", ctypes.c_int32),
+        ("max_position", ctypes.c_float),
+        ("min_position", ctypes.c_float),
+        ("max_abs_velocity", ctypes.c_float),
+        ("argmax_abs_velocity", ctypes.c_int32),
+        ("position_ok", ctypes.c_int32),
+        ("velocity_ok", ctypes.c_int32),
+        ("pad_", ctypes.c_int32),
+    ]
+
+
+DENSE_REPORT_FIELDS = [f[0] for f in IrmDenseReport._fields_ if f[0] != "pad_"]
+
+
 # name -> (restype, argtypes); every symbol include/irm.h declares.
 PROTOTYPES = {
     "irm_params_default": (None, [ctypes.POINTER(IrmParams)]),
@@ -177,6 +196,22 @@ PROTOTYPES = {
     ),
     "irm_set_work_queue": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
     "irm_work_queue_groups": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "irm_query_matrices": (
+        ctypes.c_int, [ctypes.c_int32, ctypes.c_float, c_float_p, ctypes.c_int32, c_float_p, c_float_p]
+    ),
+    "irm_set_eval_times": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32]),
+    "irm_eval_times": (ctypes.c_int32, [ctypes.c_void_p, c_float_p]),
+    "irm_eval_any": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32, ctypes.c_int32, c_float_p]),
+    "irm_dense_check": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+         ctypes.POINTER(IrmDenseReport), c_float_p],
+    ),
+    "irm_dense_check_dev": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+         ctypes.POINTER(IrmDenseReport), c_float_p, ctypes.c_void_p],
+    ),
     "irm_build_id": (ctypes.c_char_p, []),
     "irm_debug_phase_profile": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
     "irm_debug_bls_trace_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),

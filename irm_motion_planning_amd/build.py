@@ -109,6 +109,8 @@ def _units():
     # the work queue's kernels in units of their own: the opt_fix* units and their objects stay as they are
     u += [(f"opt_fixq{d}_{n}", "irm_opt_inst.hip", [f"-DIRM_INST_FIXQ_D={d}", f"-DIRM_INST_FIXQ_N={n}"])
           for d, n in QUEUE_SHAPES]
+    # evaluation at arbitrary times (irm_eval_any, irm_dense_check): kernels and launchers of their own
+    u += [("irm_dense", "irm_dense.hip", [])]
     return u
 
 

@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _abi
-from ._abi import IrmBatchDev, IrmInfo, IrmLaunchPlan, IrmParams, IrmStats, check, load_library
+from ._abi import IrmBatchDev, IrmDenseReport, IrmInfo, IrmLaunchPlan, IrmParams, IrmStats, check, load_library
 
 _fp = _abi.c_float_p
 
@@ -144,6 +144,62 @@ class Context:
         out = np.zeros_like(a)
         check(self.lib.irm_evaluate(self._h, _ptr(a), a.shape[0], int(which), _ptr(out)))
         return out[0] if single else out
+
+    # ------------------------------------------- evaluation at arbitrary times
+    def set_eval_times(self, t):
+        """The M times that eval_any / dense_check evaluate at (irm_set_eval_times: builds and uploads the
+        query matrices; replaces the previous grid).  Any finite times, in any order."""
+        t = _f32(t).reshape(-1)
+        check(self.lib.irm_set_eval_times(self._h, _ptr(t), t.shape[0]))
+
+    def eval_times(self):
+        """The evaluation times currently set (empty if none)."""
+        m = self.lib.irm_eval_times(self._h, None)
+        if m < 0:
+            check(m)
+        t = np.zeros(m, np.float32)
+        if m:
+            self.lib.irm_eval_times(self._h, _ptr(t))
+        return t
+
+    def eval_any(self, alpha, which=0):
+        """Positions (which 0) or velocities (which 1) at the evaluation times, (B×)M×D — trajectory.py:68-70."""
+        a, single = self._batch(alpha, (self.N, self.D))
+        M = int(self.lib.irm_eval_times(self._h, None))
+        out = np.zeros((a.shape[0], max(M, 0), self.D), np.float32)
+        check(self.lib.irm_eval_any(self._h, _ptr(a), a.shape[0], int(which), _ptr(out)))
+        return out[0] if single else out
+
+    def dense_check(self, alpha, obstacles, with_cost=False):
+        """Obstacle cost, joint and velocity limits on the evaluation times (irm_dense_check): a dict of
+        arrays named as irm_dense_report's fields, plus `cost` ((B×)M per-sample cost) with with_cost.
+        obstacles: (O, 2) shared, or (B, O, 2) one table per problem, like optimize."""
+        a, single = self._batch(alpha, (self.N, self.D))
+        B = a.shape[0]
+        obs = _f32(obstacles)
+        O = obs.shape[-2] if obs.size else 0
+        stride = 0
+        if obs.ndim == 3:
+            if obs.shape[0] != B or obs.shape[2] != 2:
+                raise ValueError(f"per-problem obstacles must be ({B}, O, 2), got {obs.shape}")
+            stride = 2 * O
+        elif obs.size and (obs.ndim != 2 or obs.shape[1] != 2):
+            raise ValueError(f"shared obstacles must be (O, 2), got {obs.shape}")
+        M = int(self.lib.irm_eval_times(self._h, None))
+        rep = (IrmDenseReport * B)()
+        cost = np.zeros((B, max(M, 0)), np.float32) if with_cost else None
+        check(self.lib.irm_dense_check(self._h, _ptr(a), _ptr(obs), O, stride, B, rep, _ptr(cost)))
+        out = {}
+        recs = np.frombuffer(rep, dtype=np.dtype(
+            [(name, np.float32 if ctype is ctypes.c_float else np.int32) for name, ctype in IrmDenseReport._fields_]))
+        for name in _abi.DENSE_REPORT_FIELDS:
+            vals = recs[name].copy()
+            if name.endswith("_ok"):
+                vals = vals.astype(bool)
+            out[name] = vals[0] if single else vals
+        if with_cost:
+            out["cost"] = cost[0] if single else cost
+        return out
 
     def _sg(self, start, goal, B):
         s = _f32(np.broadcast_to(_f32(start), (B, self.D)))

@@ -278,6 +278,32 @@ void fill_frag(std::vector<float>& out, int M, int K, const std::vector<double>&
 
 int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+// t = jnp.linspace(0, 1, N) in fp32 (trajectory.py:35)
+void support_times(int N, float* t) {
+    const float div = (float)(N - 1);
+    for (int i = 0; i < N - 1; ++i) {
+        const float st = (float)i / div;
+        t[i] = 0.f * (1.f - st) + 1.f * st;
+    }
+    t[N - 1] = 1.f;
+}
+
+// Kernel matrices of M evaluation times against N support times (M×N, row = evaluation time; outputs
+// nullable): entry (i, j) = kernel_f(support[j], eval[i]) in fp32 as the reference evaluates km / dkm
+// (trajectory.py:14-19, 40-48) — K and dK themselves for eval = support (the context's), the query
+// matrices of eval_any for any other grid, the same arithmetic by construction.
+void kernel_matrices(const float* support, int N, float rbf_variance, const float* eval, int M, float* km, float* dkm) {
+    const double sig = decimal_double(rbf_variance);
+    const float two_s2 = (float)(2.0 * sig * sig), s2 = (float)(sig * sig);
+    for (int i = 0; i < M; ++i)
+        for (int j = 0; j < N; ++j) {
+            const float d = support[j] - eval[i];
+            const float e = expf(-(d * d) / two_s2);
+            if (km) km[(size_t)i * N + j] = e;
+            if (dkm) dkm[(size_t)i * N + j] = d / s2 * e;
+        }
+}
+
 }  // namespace
 
 // ================================================================ context
@@ -308,6 +334,10 @@ struct irm_ctx {
     float* d_trace = nullptr;  // BLS line-search log of problem 0 (irm_debug_bls_trace)
     int trace_cap = 0;
     int32_t* d_queue = nullptr;  // the work queue's problem counter (kp.queue; the request is kp.queue_groups)
+    // evaluation times of irm_eval_any / irm_dense_check (irm_set_eval_times) and their query matrices on
+    // the device, transposed ([N][M])
+    std::vector<float> t_eval;
+    float *d_KqT = nullptr, *d_dKqT = nullptr;
 };
 
 namespace {
@@ -506,31 +536,14 @@ int irm_ctx_create(irm_ctx** out, const irm_params* p) {
     // ---- Trajectory.__init__ (trajectory.py:31-42), fp32 as the reference
     c->t.resize(N);
     c->cvec.resize(N);
-    {
-        const float div = (float)(N - 1);
-        for (int i = 0; i < N - 1; ++i) {
-            const float st = (float)i / div;
-            c->t[i] = 0.f * (1.f - st) + 1.f * st;
-        }
-        c->t[N - 1] = 1.f;
-        for (int i = 0; i < N; ++i) {
-            const float tt = c->t[i], t3 = tt * tt * tt, t4 = t3 * tt, t5 = t4 * tt;
-            c->cvec[i] = 6.f * t5 - 15.f * t4 + 10.f * t3;
-        }
+    support_times(N, c->t.data());
+    for (int i = 0; i < N; ++i) {
+        const float tt = c->t[i], t3 = tt * tt * tt, t4 = t3 * tt, t5 = t4 * tt;
+        c->cvec[i] = 6.f * t5 - 15.f * t4 + 10.f * t3;
     }
     c->K.resize((size_t)N * N);
     c->dK.resize((size_t)N * N);
-    {
-        const double sig = decimal_double(p->rbf_variance);
-        const float two_s2 = (float)(2.0 * sig * sig), s2 = (float)(sig * sig);
-        for (int i = 0; i < N; ++i)
-            for (int j = 0; j < N; ++j) {
-                const float d = c->t[j] - c->t[i];
-                const float e = expf(-(d * d) / two_s2);
-                c->K[(size_t)i * N + j] = e;
-                c->dK[(size_t)i * N + j] = d / s2 * e;
-            }
-    }
+    kernel_matrices(c->t.data(), N, p->rbf_variance, c->t.data(), N, c->K.data(), c->dK.data());
     c->J.assign(p->jac, p->jac + (size_t)D * D);
 
     // ---- operator factorisation F = L·V_R
@@ -927,6 +940,8 @@ void irm_ctx_destroy(irm_ctx* c) {
     if (c->d_prof) (void)hipFree(c->d_prof);
     if (c->d_trace) (void)hipFree(c->d_trace);
     if (c->d_queue) (void)hipFree(c->d_queue);
+    if (c->d_KqT) (void)hipFree(c->d_KqT);
+    if (c->d_dKqT) (void)hipFree(c->d_dKqT);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1283,6 +1298,133 @@ int irm_work_queue_groups(const irm_ctx* c, int32_t batch, int32_t n_obstacles, 
     d.describe_only = true;
     HIP_TRY(irm::launch_optimize(kp, nullptr, &d));  // the dispatch fills d and launches nothing
     return d.queue_groups;
+}
+
+// ------------------------------------------- evaluation at arbitrary times
+}  // extern "C"
+
+namespace {
+
+int check_eval_times(const char* fn, const float* t_eval, int M) {
+    if (!t_eval) return fail(IRM_EINVAL, "%s: null t_eval", fn);
+    if (M < 1 || M > IRM_MAX_EVAL_TIMES) return fail(IRM_EINVAL, "%s: M=%d outside [1, %d]", fn, M, IRM_MAX_EVAL_TIMES);
+    for (int i = 0; i < M; ++i)
+        if (!std::isfinite(t_eval[i])) return fail(IRM_EINVAL, "%s: t_eval[%d] is not finite", fn, i);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int irm_query_matrices(int32_t N, float rbf_variance, const float* t_eval, int32_t M, float* kq, float* dkq) {
+    if (N < 2 || N > IRM_MAX_TIMESTEPS)
+        return fail(IRM_EINVAL, "irm_query_matrices: n_timesteps=%d outside [2, %d]", N, IRM_MAX_TIMESTEPS);
+    if (!(rbf_variance > 0.f)) return fail(IRM_EINVAL, "irm_query_matrices: rbf_variance must be > 0");
+    if (check_eval_times("irm_query_matrices", t_eval, M)) return IRM_EINVAL;
+    std::vector<float> t(N);
+    support_times(N, t.data());
+    kernel_matrices(t.data(), N, rbf_variance, t_eval, M, kq, dkq);
+    return IRM_OK;
+}
+
+int irm_set_eval_times(irm_ctx* c, const float* t_eval, int32_t M) {
+    if (!c) return fail(IRM_EINVAL, "irm_set_eval_times: null context");
+    if (check_eval_times("irm_set_eval_times", t_eval, M)) return IRM_EINVAL;
+    if (set_device(c)) return IRM_EDEVICE;
+    const int N = c->N;
+    std::vector<float> kq((size_t)M * N), dkq((size_t)M * N), kqT((size_t)N * M), dkqT((size_t)N * M);
+    kernel_matrices(c->t.data(), N, c->p.rbf_variance, t_eval, M, kq.data(), dkq.data());
+    for (int i = 0; i < M; ++i)
+        for (int j = 0; j < N; ++j) {
+            kqT[(size_t)j * M + i] = kq[(size_t)i * N + j];
+            dkqT[(size_t)j * M + i] = dkq[(size_t)i * N + j];
+        }
+    // (hipFree waits for the device: no launch that reads the previous grid is left running)
+    if (c->d_KqT) (void)hipFree(c->d_KqT);
+    if (c->d_dKqT) (void)hipFree(c->d_dKqT);
+    c->d_KqT = c->d_dKqT = nullptr;
+    c->t_eval.clear();
+    if (upload(&c->d_KqT, kqT) || upload(&c->d_dKqT, dkqT)) return IRM_ENOMEM;
+    c->t_eval.assign(t_eval, t_eval + M);
+    return IRM_OK;
+}
+
+int32_t irm_eval_times(const irm_ctx* c, float* t_out) {
+    if (!c) return fail(IRM_EINVAL, "irm_eval_times: null context");
+    if (t_out && !c->t_eval.empty()) memcpy(t_out, c->t_eval.data(), sizeof(float) * c->t_eval.size());
+    return (int32_t)c->t_eval.size();
+}
+
+int irm_eval_any(irm_ctx* c, const float* alpha, int32_t B, int32_t which, float* out) {
+    if (!c || !alpha || !out) return fail(IRM_EINVAL, "irm_eval_any: null argument");
+    if (c->t_eval.empty()) return fail(IRM_EINVAL, "irm_eval_any: no evaluation times set (irm_set_eval_times)");
+    if (B < 0) return fail(IRM_EINVAL, "irm_eval_any: negative batch");
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    const int N = c->N, D = c->D, M = (int)c->t_eval.size();
+    const size_t nd = (size_t)B * N * D, md = (size_t)B * M * D;
+    Stage st{c};
+    const size_t o_a = st.take(nd * 4), o_o = st.take(md * 4);
+    if (ensure_io(c, st.off)) return IRM_ENOMEM;
+    char* d = st.base();
+    hipStream_t s = c->stream;
+    KParams kp = c->kp;
+    kp.B = B;
+    kp.alpha0 = (const float*)(d + o_a);
+    HIP_TRY(hipMemcpyAsync(d + o_a, alpha, nd * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(irm::launch_eval_any(kp, which ? c->d_dKqT : c->d_KqT, M, (float*)(d + o_o), s));
+    HIP_TRY(hipMemcpyAsync(out, d + o_o, md * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return IRM_OK;
+}
+
+int irm_dense_check_dev(irm_ctx* c, const float* alpha, const float* obstacles, int32_t O, int32_t obstacle_stride,
+                        int32_t B, irm_dense_report* report, float* cost, void* stream) {
+    if (!c || !alpha || !report) return fail(IRM_EINVAL, "irm_dense_check_dev: null argument");
+    if (c->t_eval.empty()) return fail(IRM_EINVAL, "irm_dense_check_dev: no evaluation times set (irm_set_eval_times)");
+    if (B < 0) return fail(IRM_EINVAL, "irm_dense_check_dev: negative batch");
+    if (check_obs(O) || check_stride(O, obstacle_stride)) return IRM_EINVAL;
+    if (O > 0 && !obstacles) return fail(IRM_EINVAL, "irm_dense_check_dev: obstacles pointer missing");
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    KParams kp = c->kp;
+    kp.B = B;
+    kp.O = O;
+    kp.obs_stride = obstacle_stride;
+    kp.alpha0 = alpha;
+    kp.obstacles = obstacles;
+    HIP_TRY(irm::launch_dense_check(kp, c->d_KqT, c->d_dKqT, (int)c->t_eval.size(), report, cost, (hipStream_t)stream));
+    return IRM_OK;
+}
+
+int irm_dense_check(irm_ctx* c, const float* alpha, const float* obstacles, int32_t O, int32_t obstacle_stride,
+                    int32_t B, irm_dense_report* report_out, float* cost_out) {
+    if (!c || !alpha || !report_out) return fail(IRM_EINVAL, "irm_dense_check: null argument");
+    if (c->t_eval.empty()) return fail(IRM_EINVAL, "irm_dense_check: no evaluation times set (irm_set_eval_times)");
+    if (B < 0) return fail(IRM_EINVAL, "irm_dense_check: negative batch");
+    if (check_obs(O) || check_stride(O, obstacle_stride)) return IRM_EINVAL;
+    if (O > 0 && !obstacles) return fail(IRM_EINVAL, "irm_dense_check: obstacles pointer missing");
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    const int N = c->N, D = c->D, M = (int)c->t_eval.size();
+    const size_t nd = (size_t)B * N * D;
+    const size_t nobs = obstacle_stride ? (size_t)B * obstacle_stride : (size_t)O * 2;
+    Stage st{c};
+    const size_t o_a = st.take(nd * 4), o_o = st.take(std::max<size_t>(nobs, 1) * 4),
+                 o_r = st.take((size_t)B * sizeof(irm_dense_report)), o_c = st.take((size_t)B * M * 4);
+    if (ensure_io(c, st.off)) return IRM_ENOMEM;
+    char* d = st.base();
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d + o_a, alpha, nd * 4, hipMemcpyHostToDevice, s));
+    if (nobs && O > 0) HIP_TRY(hipMemcpyAsync(d + o_o, obstacles, nobs * 4, hipMemcpyHostToDevice, s));
+    const int rc = irm_dense_check_dev(c, (const float*)(d + o_a), (const float*)(d + o_o), O, obstacle_stride, B,
+                                       (irm_dense_report*)(d + o_r), cost_out ? (float*)(d + o_c) : nullptr, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(report_out, d + o_r, (size_t)B * sizeof(irm_dense_report), hipMemcpyDeviceToHost, s));
+    if (cost_out) HIP_TRY(hipMemcpyAsync(cost_out, d + o_c, (size_t)B * M * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return IRM_OK;
 }
 
 const char* irm_build_id(void) {

@@ -338,5 +338,10 @@ hipError_t launch_forward(const KParams& p, int mode, hipStream_t s);  // mode: 
 hipError_t launch_fk(const KParams& p, const float* traj, float* pos, float* jac, hipStream_t s);
 hipError_t launch_fk_joints(const KParams& p, const float* traj, float* pos, hipStream_t s);
 hipError_t launch_cost_vg(const KParams& p, const float* f, float* cv, float* cg, hipStream_t s);
+// irm_dense.hip — evaluation at arbitrary times.  mT / kqT / dkqT: query matrices on the device, transposed
+// ([N][M]); α from p.alpha0 (B×N×D), obstacles from p.obstacles / p.O / p.obs_stride.
+hipError_t launch_eval_any(const KParams& p, const float* mT, int M, float* out, hipStream_t s);
+hipError_t launch_dense_check(const KParams& p, const float* kqT, const float* dkqT, int M, irm_dense_report* rep,
+                              float* cost, hipStream_t s);
 
 }  // namespace irm

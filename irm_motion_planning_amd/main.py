@@ -7,7 +7,8 @@ the stdout lines ("setup object, jit-compile took", "took X ms",
 files trajectory_result.txt / trajectory_series.txt (np.savetxt defaults).
 
 Additive flags (no reference counterpart): --batch-size, --seed,
---operator-rank, --device, --whole-robot-cost, --work-queue.
+--operator-rank, --device, --whole-robot-cost, --work-queue, --dense-check
+(which adds one stdout line and trajectory_result_dense.txt).
 """
 import argparse
 import os
@@ -123,11 +124,43 @@ def build_parser():
                         help="Batched path: run N persistent workgroups (auto: as many as the GPU holds) whose "
                              "finished slots claim the next problem, instead of one workgroup per fixed group of "
                              "problems; same results (default: off)")
+    parser.add_argument('--dense-check', type=_sample_count, default=0, metavar='M',
+                        help="After the report, evaluate the result on linspace(0, 1, M) — between the waypoints "
+                             "the optimiser looked at — and print its obstacle cost, joint and velocity limits "
+                             "there; writes trajectory_result_dense.txt (default: 0 = off)")
     return parser
+
+
+def _sample_count(x):
+    """--dense-check: a number of samples ≥ 0."""
+    word = str(x).strip()
+    if not word.isdigit():
+        raise argparse.ArgumentTypeError(f"expected a sample count >= 0, got {x!r}")
+    return int(word)
 
 
 def parse_args(argv=None):
     return build_parser().parse_args(argv)
+
+
+DENSE_RESULT = "trajectory_result_dense.txt"
+
+
+def dense_report(context, alpha, obstacles, M):
+    """--dense-check M: the result on linspace(0, 1, M).  Prints problem 0's line, writes its M×D positions
+    and returns the batch's report (Context.dense_check)."""
+    t = np.linspace(0, 1, M, dtype=np.float32)
+    context.set_eval_times(t)
+    alpha = np.asarray(alpha, np.float32)
+    rep = context.dense_check(alpha, obstacles)
+    first = {k: (v if alpha.ndim == 2 else v[0]) for k, v in rep.items()}
+    f32 = np.float32
+    print(f"dense check ({M} samples): max cost", f32(first["max_cost"]), "at t=" + str(t[int(first["argmax_cost"])]) + ";",
+          "joint limit", "ok" if first["position_ok"] else "exceeded", "with", f32(first["max_position"]),
+          str(f32(first["min_position"])) + ";",
+          "velocity limit", "ok" if first["velocity_ok"] else "exceeded", "with", f32(first["max_abs_velocity"]))
+    np.savetxt(DENSE_RESULT, context.eval_any(alpha if alpha.ndim == 2 else alpha[0], 0))
+    return rep
 
 
 def run_batch(optimizer, args):
@@ -195,6 +228,12 @@ def run_batch(optimizer, args):
           "; inner iterations", int(np.sum(stats["inner_iterations"])))
     ok0 = tr.constraintsFulfilledVerbose(alpha[0], start[0], goal[0], verbose=True)
     print("result cost: ( avg", avg[0], ", max", mx[0], "). constraint fulfiled", ok0)
+    if getattr(args, "dense_check", 0) > 0:
+        rep = dense_report(optimizer.context, alpha, env.obstacles, args.dense_check)
+        dense_ok = rep["position_ok"] & rep["velocity_ok"]
+        print("dense check:", int(np.sum(np.asarray(ok, bool) & ~dense_ok)), "of", int(np.sum(ok)),
+              "problems that fulfil the constraints on the support grid exceed a joint or velocity limit between "
+              "the waypoints")
     batch_io.write_result(batch_io.RESULT, traj[0])
     batch_io.write_result_batch(batch_io.RESULT_BATCH, traj)
     batch_io.write_summary(batch_io.SUMMARY_BATCH, avg, mx, ok, stats)
@@ -263,6 +302,8 @@ def main(argv=None):
 
     np_trajectory = np.array(tr.evaluate(result_alpha, tr.km, tr.jac))
     np.savetxt("trajectory_result.txt", np_trajectory)
+    if args.dense_check > 0:
+        dense_report(optimizer.context, result_alpha, env.obstacles, args.dense_check)
     if args.extended_vis:
         p_np = np.array(p)
         print(p_np.shape)

@@ -5,6 +5,7 @@ mean/std_joint_position) and the same public methods with the same argument
 meaning; every method runs a HIP kernel through the C ABI:
 
   evaluate                    trajectory.py:63-65   irm_evaluate
+  eval_any                    trajectory.py:68-70   irm_set_eval_times + irm_eval_any
   initTrajectory              trajectory.py:73-78   irm_init_alpha
   compute_trajectory_cost     trajectory.py:271-281 irm_eval_cost
   compute_trajectory_cost_g   trajectory.py:284-297 irm_eval_cost_grad
@@ -17,6 +18,16 @@ import numpy as np
 from .context import Context
 from .params import params_from_args
 from .robot import Robot
+
+
+def rbf_kernel(x_1, x_2, rbf_var):
+    """trajectory.py:14-15."""
+    return np.exp(-(x_1 - x_2) ** 2 / (2 * rbf_var ** 2))
+
+
+def d_rbf_kernel(x_1, x_2, rbf_var):
+    """trajectory.py:18-19."""
+    return (x_1 - x_2) / (rbf_var ** 2) * np.exp(-(x_1 - x_2) ** 2 / (2 * rbf_var ** 2))
 
 
 class Trajectory:
@@ -50,6 +61,26 @@ class Trajectory:
         else:
             raise ValueError("evaluate: kernel_matrix must be this trajectory's km or dkm")
         return self.context.evaluate(alpha, which)
+
+    def eval_any(self, alpha, kernel_f, support_x, eval_x, jac):
+        """K(·, eval_x) @ alpha @ jac (kernel_f = rbf_kernel) or its time derivative (d_rbf_kernel) at any
+        times eval_x — trajectory.py:68-70 with the reference's signature.  Row i of the result is time
+        eval_x[i]; eval_x = self.t gives evaluate(alpha, self.km / self.dkm, jac) to the bit.  The grid is
+        uploaded only when eval_x differs from the one the context holds."""
+        if kernel_f is rbf_kernel:
+            which = 0
+        elif kernel_f is d_rbf_kernel:
+            which = 1
+        else:
+            raise ValueError("eval_any: kernel_f must be this module's rbf_kernel or d_rbf_kernel")
+        if support_x is not self.t and not np.array_equal(np.asarray(support_x), self.t):
+            raise ValueError("eval_any: only this trajectory's support times t are supported")
+        if jac is not self.jac and not np.array_equal(np.asarray(jac), self.jac):
+            raise ValueError("eval_any: only this trajectory's J is supported")
+        x = np.ascontiguousarray(eval_x, dtype=np.float32).reshape(-1)
+        if not np.array_equal(x, self.context.eval_times()):
+            self.context.set_eval_times(x)
+        return self.context.eval_any(alpha, which)
 
     def initTrajectory(self, start_config, goal_config):
         return self.context.init_alpha(start_config, goal_config)
