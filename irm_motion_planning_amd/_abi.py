@@ -17,6 +17,7 @@ IRM_MAX_TIMESTEPS = 512
 IRM_MAX_OBSTACLES = 64
 IRM_MAX_LR = 32
 IRM_MAX_EVAL_TIMES = 4096
+IRM_FIT_RIDGE_DEFAULT = 1e-6
 
 IRM_OPT_GD = 0
 IRM_OPT_BLS = 1
@@ -24,6 +25,7 @@ IRM_OPT_BLS = 1
 c_float_p = ctypes.POINTER(ctypes.c_float)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
 c_uint8_p = ctypes.POINTER(ctypes.c_uint8)
+c_double_p = ctypes.POINTER(ctypes.c_double)
 
 
 class IrmError(RuntimeError):
@@ -211,6 +213,21 @@ PROTOTYPES = {
         ctypes.c_int,
         [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
          ctypes.POINTER(IrmDenseReport), c_float_p, ctypes.c_void_p],
+    ),
+    "irm_fit_operator": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
+         ctypes.c_float, c_double_p],
+    ),
+    "irm_set_fit_ridge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float]),
+    "irm_fit_alpha": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32, c_float_p]),
+    "irm_set_transfer": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float]
+    ),
+    "irm_transfer_alpha": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32, c_float_p, c_float_p]),
+    "irm_fit_alpha_dev": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32, c_float_p, ctypes.c_void_p]),
+    "irm_transfer_alpha_dev": (
+        ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32, c_float_p, c_float_p, ctypes.c_void_p]
     ),
     "irm_build_id": (ctypes.c_char_p, []),
     "irm_debug_phase_profile": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),

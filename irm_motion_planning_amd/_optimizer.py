@@ -60,6 +60,26 @@ class _PersistentOptimizer:
         self.last_trajectory = traj
         return alpha
 
+    def coarse_to_fine(self, coarse, start, goal, obstacles=None, series=False):
+        """Coarse-to-fine optimize_batch(): solve the B problems on the support grid of `coarse` (a Context
+        of the same hyper-parameters and another --n-timesteps), carry that solution onto this optimizer's
+        grid (Context.set_transfer / transfer_alpha) and optimise from it.
+
+        Returns optimize_batch()'s result of the fine stage; self.last_stages keeps both stages:
+        {"coarse": {"n_timesteps", "alpha", "stats"}, "fine": {"n_timesteps", "alpha0", "stats"}}."""
+        obstacles = self.env.obstacles if obstacles is None else obstacles
+        D = self.trajectory.robot.N_joints
+        start = np.asarray(start, np.float32).reshape(-1, D)
+        goal = np.asarray(goal, np.float32).reshape(-1, D)
+        a_c, _, st_c = coarse.optimize(start, goal, obstacles)
+        self.context.set_transfer(coarse.N, rbf_variance_src=coarse.params.rbf_variance)
+        alpha0 = self.context.transfer_alpha(a_c)
+        res = self.context.optimize(start, goal, obstacles, alpha0=alpha0, series=series)
+        self.last_stats = res[2]
+        self.last_stages = {"coarse": {"n_timesteps": coarse.N, "alpha": a_c, "stats": st_c},
+                            "fine": {"n_timesteps": self.context.N, "alpha0": alpha0, "stats": res[2]}}
+        return res
+
     def optimize_batch(self, start, goal, obstacles=None, alpha0=None, obstacle_stride=0, series=False):
         """Batched optimize(): B independent start/goal problems (B×D each).
 

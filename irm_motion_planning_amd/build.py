@@ -111,6 +111,8 @@ def _units():
           for d, n in QUEUE_SHAPES]
     # evaluation at arbitrary times (irm_eval_any, irm_dense_check): kernels and launchers of their own
     u += [("irm_dense", "irm_dense.hip", [])]
+    # fitting and re-timing (irm_fit_alpha, irm_transfer_alpha): kernels and launchers of their own
+    u += [("irm_fit", "irm_fit.hip", [])]
     return u
 
 

@@ -23,6 +23,27 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(_fp)
 
 
+def _dev(addr):
+    """A raw device address as the float* the *_dev entry points take (0 / None: NULL)."""
+    return ctypes.cast(ctypes.c_void_p(int(addr) if addr else None), _fp)
+
+
+def fit_operator(n_timesteps, rbf_variance=0.1, ridge=_abi.IRM_FIT_RIDGE_DEFAULT, n_src=0, rbf_variance_src=None,
+                 t0=0.0, t1=1.0):
+    """The fp64 operators of fit_alpha / transfer_alpha as the library builds them (irm_fit_operator; host only, no
+    context, no device): W = (K + ρI)⁻¹ (N×N) for n_src = 0, else T = W·Kx (N×n_src) for the source grid
+    linspace(0, 1, n_src), its kernel width (None: rbf_variance) and the time map [0, 1] → [t0, t1]."""
+    lib = load_library()
+    N, M = int(n_timesteps), int(n_src)
+    out = np.zeros((max(N, 0), max(M, 0) if M else max(N, 0)), np.float64)
+    if out.size == 0:
+        out = np.zeros((1, 1), np.float64)  # (bad sizes: the library refuses them before it writes)
+    var_src = -1.0 if rbf_variance_src is None else float(rbf_variance_src)
+    check(lib.irm_fit_operator(N, float(rbf_variance), float(ridge), M, var_src, float(t0), float(t1),
+                               out.ctypes.data_as(_abi.c_double_p)))
+    return out
+
+
 def stats_to_dict(stats):
     out = {name: np.array([getattr(s, name) for s in stats]) for name in _abi.STATS_FIELDS}
     return out
@@ -200,6 +221,56 @@ class Context:
         if with_cost:
             out["cost"] = cost[0] if single else cost
         return out
+
+    # ------------------------------------------------- fitting and re-timing
+    def set_fit_ridge(self, ridge):
+        """The ridge ρ of every later fit_alpha / transfer_alpha (irm_set_fit_ridge: rebuilds W = (K + ρI)⁻¹ and
+        drops a transfer that was set).  Raises IrmError where K + ρI is not positive definite (ρ below ≈ 1e-6)."""
+        check(self.lib.irm_set_fit_ridge(self._h, float(ridge)))
+
+    def fit_alpha(self, traj):
+        """α whose trajectory is the ridge fit of the waypoints traj ((B×)N×D on this context's support times) —
+        irm_fit_alpha: the way into the optimiser from a recorded path or another planner's output."""
+        q, single = self._batch(traj, (self.N, self.D))
+        out = np.zeros_like(q)
+        check(self.lib.irm_fit_alpha(self._h, _ptr(q), q.shape[0], _ptr(out)))
+        return out[0] if single else out
+
+    def set_transfer(self, n_src, t0=0.0, t1=1.0, rbf_variance_src=None):
+        """The operator of transfer_alpha (irm_set_transfer): from a source grid of n_src support times
+        linspace(0, 1, n_src) with kernel width rbf_variance_src (None: this context's), re-timed so that
+        this context's [0, 1] is the source's [t0, t1].  Replaces the previous transfer."""
+        var = -1.0 if rbf_variance_src is None else float(rbf_variance_src)
+        check(self.lib.irm_set_transfer(self._h, int(n_src), var, float(t0), float(t1)))
+        self._n_src = int(n_src)
+
+    def transfer_alpha(self, alpha_src, with_start=False):
+        """α on this context's grid from alpha_src ((B×)n_src×D) on the source grid (irm_transfer_alpha).  With
+        with_start also the source trajectory at t0 ((B×)D): the start configuration of the re-timed plan."""
+        n_src = getattr(self, "_n_src", 0)  # (0: no transfer set — the library refuses before it reads anything)
+        a = _f32(alpha_src)
+        single = a.ndim == 2
+        if single:
+            a = a[None]
+        if n_src and (a.ndim != 3 or a.shape[1:] != (n_src, self.D)):
+            raise _abi.IrmError(f"alpha_src must be (B, {n_src}, {self.D}) for the transfer that is set, got {a.shape}")
+        B = a.shape[0]
+        out = np.zeros((B, self.N, self.D), np.float32)
+        start = np.zeros((B, self.D), np.float32) if with_start else None
+        check(self.lib.irm_transfer_alpha(self._h, _ptr(a), B, _ptr(out), _ptr(start)))
+        if single:
+            out = out[0]
+            start = None if start is None else start[0]
+        return (out, start) if with_start else out
+
+    def fit_alpha_dev(self, traj_dev, batch, alpha_dev, stream=0):
+        """Enqueue irm_fit_alpha_dev with raw device addresses (e.g. torch data_ptr())."""
+        check(self.lib.irm_fit_alpha_dev(self._h, _dev(traj_dev), int(batch), _dev(alpha_dev), ctypes.c_void_p(stream)))
+
+    def transfer_alpha_dev(self, alpha_src_dev, batch, alpha_dev, start_dev=0, stream=0):
+        """Enqueue irm_transfer_alpha_dev with raw device addresses; start_dev 0: no start output."""
+        check(self.lib.irm_transfer_alpha_dev(self._h, _dev(alpha_src_dev), int(batch), _dev(alpha_dev),
+                                              _dev(start_dev), ctypes.c_void_p(stream)))
 
     def _sg(self, start, goal, B):
         s = _f32(np.broadcast_to(_f32(start), (B, self.D)))

@@ -338,6 +338,14 @@ struct irm_ctx {
     // the device, transposed ([N][M])
     std::vector<float> t_eval;
     float *d_KqT = nullptr, *d_dKqT = nullptr;
+    // fitting and re-timing (irm_fit_alpha, irm_transfer_alpha): the ridge ρ, the Cholesky factor of K + ρI
+    // (extended precision, see fit_factor; empty until first use), Wᵀ and Tᵀ on the device in fp64 ([source row][waypoint]) and the source grid's
+    // fp32 query row at t0 (xfer_src = 0: no transfer set)
+    float fit_ridge = IRM_FIT_RIDGE_DEFAULT;
+    std::vector<long double> fit_L;
+    double *d_WT = nullptr, *d_TT = nullptr;
+    float* d_kq0 = nullptr;
+    int xfer_src = 0;
 };
 
 namespace {
@@ -942,6 +950,9 @@ void irm_ctx_destroy(irm_ctx* c) {
     if (c->d_queue) (void)hipFree(c->d_queue);
     if (c->d_KqT) (void)hipFree(c->d_KqT);
     if (c->d_dKqT) (void)hipFree(c->d_dKqT);
+    if (c->d_WT) (void)hipFree(c->d_WT);
+    if (c->d_TT) (void)hipFree(c->d_TT);
+    if (c->d_kq0) (void)hipFree(c->d_kq0);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1423,6 +1434,300 @@ int irm_dense_check(irm_ctx* c, const float* alpha, const float* obstacles, int3
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(report_out, d + o_r, (size_t)B * sizeof(irm_dense_report), hipMemcpyDeviceToHost, s));
     if (cost_out) HIP_TRY(hipMemcpyAsync(cost_out, d + o_c, (size_t)B * M * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return IRM_OK;
+}
+
+// ------------------------------------------------- fitting and re-timing
+}  // extern "C"
+
+namespace {
+
+// The factorisation runs in extended precision (x87 long double, 64-bit significand) and its results are
+// rounded to fp64 once.  K + ρI has condition ≈ ‖K‖/ρ ≈ 1e8, and an fp64 factorisation leaves W with a forward
+// error of 1e-8·‖W‖: a W that is symmetric by construction (L⁻ᵀ·L⁻¹) then misses (K + ρI)·W = I by 150-250
+// times what an unsymmetric column-by-column solve leaves, and that solve's W is unsymmetric by 2e-4 to 5e-2
+// (N = 50 … 512).  With the factor 2048 of the wider significand both residuals are the final rounding's.
+typedef long double fit_real;
+
+// Cholesky factor L (lower triangle, row-major n×n) of K + ρI, from the fp32 entries of K widened.
+// K is numerically singular, so ρ is what makes the matrix definite: a non-positive pivot is IRM_EINVAL.
+int fit_factor(const char* fn, const float* K, int n, float ridge, std::vector<fit_real>& L) {
+    const fit_real rho = (fit_real)ridge;
+    L.assign((size_t)n * n, (fit_real)0);
+    for (int j = 0; j < n; ++j) {
+        const fit_real* lj = &L[(size_t)j * n];
+        for (int i = j; i < n; ++i) {
+            const fit_real* li = &L[(size_t)i * n];
+            fit_real s = (fit_real)K[(size_t)i * n + j] + (i == j ? rho : (fit_real)0);
+            for (int k = 0; k < j; ++k) s -= li[k] * lj[k];
+            if (i == j) {
+                if (!(s > 0))
+                    return fail(IRM_EINVAL, "%s: K + rho*I is not positive definite for the ridge rho=%g (pivot %d of %d is %g): "
+                                "use a larger ridge (default %g)", fn, (double)rho, j, n, (double)s, (double)IRM_FIT_RIDGE_DEFAULT);
+                L[(size_t)j * n + j] = sqrtl(s);
+            } else {
+                L[(size_t)i * n + j] = s / lj[j];
+            }
+        }
+    }
+    return 0;
+}
+
+// X ← L⁻¹·X for X n×r row-major (forward substitution on every column at once).
+void fit_forward(const std::vector<fit_real>& L, int n, fit_real* X, int r) {
+    for (int i = 0; i < n; ++i) {
+        fit_real* xi = X + (size_t)i * r;
+        for (int k = 0; k < i; ++k) {
+            const fit_real l = L[(size_t)i * n + k];
+            const fit_real* xk = X + (size_t)k * r;
+            for (int j = 0; j < r; ++j) xi[j] -= l * xk[j];
+        }
+        const fit_real d = L[(size_t)i * n + i];
+        for (int j = 0; j < r; ++j) xi[j] /= d;
+    }
+}
+
+// X ← L⁻ᵀ·X.
+void fit_backward(const std::vector<fit_real>& L, int n, fit_real* X, int r) {
+    for (int i = n - 1; i >= 0; --i) {
+        fit_real* xi = X + (size_t)i * r;
+        for (int k = i + 1; k < n; ++k) {
+            const fit_real l = L[(size_t)k * n + i];
+            const fit_real* xk = X + (size_t)k * r;
+            for (int j = 0; j < r; ++j) xi[j] -= l * xk[j];
+        }
+        const fit_real d = L[(size_t)i * n + i];
+        for (int j = 0; j < r; ++j) xi[j] /= d;
+    }
+}
+
+// W = (K + ρI)⁻¹ = L⁻ᵀ·L⁻¹ (n×n): the lower triangle is summed (k ascending), rounded to fp64 and mirrored,
+// so W is symmetric to the bit.
+void fit_W(const std::vector<fit_real>& L, int n, std::vector<double>& W) {
+    std::vector<fit_real> Li((size_t)n * n, (fit_real)0), S((size_t)n * n, (fit_real)0);
+    for (int i = 0; i < n; ++i) {  // L⁻¹ (lower triangular): column j of the identity only reaches rows ≥ j
+        fit_real* xi = &Li[(size_t)i * n];
+        xi[i] = 1;
+        for (int k = 0; k < i; ++k) {
+            const fit_real l = L[(size_t)i * n + k];
+            const fit_real* xk = &Li[(size_t)k * n];
+            for (int j = 0; j <= k; ++j) xi[j] -= l * xk[j];
+        }
+        const fit_real d = L[(size_t)i * n + i];
+        for (int j = 0; j <= i; ++j) xi[j] /= d;
+    }
+    for (int k = 0; k < n; ++k) {
+        const fit_real* lk = &Li[(size_t)k * n];
+        for (int i = 0; i <= k; ++i) {
+            const fit_real a = lk[i];
+            fit_real* si = &S[(size_t)i * n];
+            for (int j = 0; j <= i; ++j) si[j] += a * lk[j];
+        }
+    }
+    W.assign((size_t)n * n, 0.0);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j <= i; ++j) W[(size_t)i * n + j] = W[(size_t)j * n + i] = (double)S[(size_t)i * n + j];
+}
+
+// T = (K + ρI)⁻¹·Kx (n×n_src) by the two triangular solves, with Kx[i][j] = rbf_kernel(t_src[j], s_i),
+// s_i = t0 + (t1 − t0)·t[i] in fp32, in kernel_matrices' fp32 arithmetic.  kq0 (nullable, n_src): Kx's row 0,
+// the source grid's query row at s_0 = t0.
+void fit_T(const std::vector<fit_real>& L, const float* t, int n, int n_src, float var_src, float t0, float t1,
+           std::vector<double>& T, float* kq0) {
+    std::vector<float> ts(n_src), s(n), kx((size_t)n * n_src);
+    support_times(n_src, ts.data());
+    const float dt = t1 - t0;
+    for (int i = 0; i < n; ++i) {
+        const float step = dt * t[i];
+        s[i] = t0 + step;
+    }
+    kernel_matrices(ts.data(), n_src, var_src, s.data(), n, kx.data(), nullptr);
+    if (kq0) memcpy(kq0, kx.data(), sizeof(float) * n_src);
+    std::vector<fit_real> X(kx.begin(), kx.end());
+    fit_forward(L, n, X.data(), n_src);
+    fit_backward(L, n, X.data(), n_src);
+    T.resize(X.size());
+    for (size_t e = 0; e < T.size(); ++e) T[e] = (double)X[e];
+}
+
+int check_ridge(const char* fn, float ridge) {
+    if (!std::isfinite(ridge) || !(ridge > 0.f)) return fail(IRM_EINVAL, "%s: the ridge rho=%g must be finite and > 0", fn, (double)ridge);
+    return 0;
+}
+
+int check_transfer(const char* fn, int n_src, float t0, float t1) {
+    if (n_src < 2 || n_src > IRM_MAX_TIMESTEPS) return fail(IRM_EINVAL, "%s: n_src=%d outside [2, %d]", fn, n_src, IRM_MAX_TIMESTEPS);
+    if (!std::isfinite(t0) || !std::isfinite(t1)) return fail(IRM_EINVAL, "%s: t0=%g, t1=%g must be finite", fn, (double)t0, (double)t1);
+    if (!(t0 < t1)) return fail(IRM_EINVAL, "%s: t0=%g must be < t1=%g", fn, (double)t0, (double)t1);
+    return 0;
+}
+
+// a (rows × cols, row-major) transposed onto the device (cols × rows).
+int upload_transposed(double** dst, const std::vector<double>& a, int rows, int cols) {
+    std::vector<double> tr((size_t)rows * cols);
+    for (int i = 0; i < rows; ++i)
+        for (int j = 0; j < cols; ++j) tr[(size_t)j * rows + i] = a[(size_t)i * cols + j];
+    HIP_TRY(hipMalloc(dst, tr.size() * sizeof(double)));
+    HIP_TRY(hipMemcpy(*dst, tr.data(), tr.size() * sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// The context's factor and Wᵀ for `ridge`, into L / d_WT (the caller owns them until it commits).
+int fit_build(const char* fn, const irm_ctx* c, float ridge, std::vector<fit_real>& L, double** d_WT) {
+    if (fit_factor(fn, c->K.data(), c->N, ridge, L)) return IRM_EINVAL;
+    std::vector<double> W;
+    fit_W(L, c->N, W);
+    *d_WT = nullptr;
+    if (upload_transposed(d_WT, W, c->N, c->N)) {
+        if (*d_WT) (void)hipFree(*d_WT);
+        *d_WT = nullptr;
+        return IRM_ENOMEM;
+    }
+    return 0;
+}
+
+// W at first use, with the context's ridge.
+int ensure_fit(const char* fn, irm_ctx* c) {
+    if (c->d_WT) return 0;
+    std::vector<fit_real> L;
+    double* w = nullptr;
+    const int rc = fit_build(fn, c, c->fit_ridge, L, &w);
+    if (rc) return rc;
+    c->fit_L.swap(L);
+    c->d_WT = w;
+    return 0;
+}
+
+void drop_transfer(irm_ctx* c) {
+    // (hipFree waits for the device: no launch that reads the previous operator is left running)
+    if (c->d_TT) (void)hipFree(c->d_TT);
+    if (c->d_kq0) (void)hipFree(c->d_kq0);
+    c->d_TT = nullptr;
+    c->d_kq0 = nullptr;
+    c->xfer_src = 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int irm_fit_operator(int32_t n, float rbf_variance, float ridge, int32_t n_src, float rbf_variance_src, float t0,
+                     float t1, double* out) {
+    if (n < 2 || n > IRM_MAX_TIMESTEPS) return fail(IRM_EINVAL, "irm_fit_operator: n=%d outside [2, %d]", n, IRM_MAX_TIMESTEPS);
+    if (!(rbf_variance > 0.f)) return fail(IRM_EINVAL, "irm_fit_operator: rbf_variance must be > 0");
+    if (!out) return fail(IRM_EINVAL, "irm_fit_operator: null output");
+    if (check_ridge("irm_fit_operator", ridge)) return IRM_EINVAL;
+    if (n_src != 0 && check_transfer("irm_fit_operator", n_src, t0, t1)) return IRM_EINVAL;
+    std::vector<float> t(n), K((size_t)n * n);
+    support_times(n, t.data());
+    kernel_matrices(t.data(), n, rbf_variance, t.data(), n, K.data(), nullptr);
+    std::vector<fit_real> L;
+    std::vector<double> A;
+    if (fit_factor("irm_fit_operator", K.data(), n, ridge, L)) return IRM_EINVAL;
+    if (n_src == 0) fit_W(L, n, A);
+    else fit_T(L, t.data(), n, n_src, rbf_variance_src > 0.f ? rbf_variance_src : rbf_variance, t0, t1, A, nullptr);
+    memcpy(out, A.data(), A.size() * sizeof(double));
+    return IRM_OK;
+}
+
+int irm_set_fit_ridge(irm_ctx* c, float ridge) {
+    if (!c) return fail(IRM_EINVAL, "irm_set_fit_ridge: null context");
+    if (check_ridge("irm_set_fit_ridge", ridge)) return IRM_EINVAL;
+    if (set_device(c)) return IRM_EDEVICE;
+    std::vector<fit_real> L;
+    double* w = nullptr;
+    const int rc = fit_build("irm_set_fit_ridge", c, ridge, L, &w);
+    if (rc) return rc;  // the previous ridge, W and transfer stay
+    drop_transfer(c);
+    if (c->d_WT) (void)hipFree(c->d_WT);
+    c->d_WT = w;
+    c->fit_L.swap(L);
+    c->fit_ridge = ridge;
+    return IRM_OK;
+}
+
+int irm_set_transfer(irm_ctx* c, int32_t n_src, float rbf_variance_src, float t0, float t1) {
+    if (!c) return fail(IRM_EINVAL, "irm_set_transfer: null context");
+    if (check_transfer("irm_set_transfer", n_src, t0, t1)) return IRM_EINVAL;
+    if (set_device(c)) return IRM_EDEVICE;
+    const int rc = ensure_fit("irm_set_transfer", c);
+    if (rc) return rc;
+    std::vector<double> T;
+    std::vector<float> kq0(n_src);
+    fit_T(c->fit_L, c->t.data(), c->N, n_src, rbf_variance_src > 0.f ? rbf_variance_src : c->p.rbf_variance, t0, t1, T,
+          kq0.data());
+    drop_transfer(c);
+    if (upload_transposed(&c->d_TT, T, c->N, n_src) || upload(&c->d_kq0, kq0)) {
+        drop_transfer(c);
+        return IRM_ENOMEM;
+    }
+    c->xfer_src = n_src;
+    return IRM_OK;
+}
+
+int irm_fit_alpha_dev(irm_ctx* c, const float* traj, int32_t B, float* alpha, void* stream) {
+    if (!c || !traj || !alpha) return fail(IRM_EINVAL, "irm_fit_alpha_dev: null argument");
+    if (B < 0) return fail(IRM_EINVAL, "irm_fit_alpha_dev: negative batch");
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    const int rc = ensure_fit("irm_fit_alpha_dev", c);
+    if (rc) return rc;
+    KParams kp = c->kp;
+    kp.B = B;
+    HIP_TRY(irm::launch_fit_alpha(kp, c->d_WT, traj, alpha, (hipStream_t)stream));
+    return IRM_OK;
+}
+
+int irm_transfer_alpha_dev(irm_ctx* c, const float* alpha_src, int32_t B, float* alpha, float* start, void* stream) {
+    if (!c || !alpha_src || !alpha) return fail(IRM_EINVAL, "irm_transfer_alpha_dev: null argument");
+    if (c->xfer_src == 0) return fail(IRM_EINVAL, "irm_transfer_alpha_dev: no transfer set (irm_set_transfer)");
+    if (B < 0) return fail(IRM_EINVAL, "irm_transfer_alpha_dev: negative batch");
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    KParams kp = c->kp;
+    kp.B = B;
+    HIP_TRY(irm::launch_transfer_alpha(kp, c->d_TT, c->xfer_src, c->d_kq0, alpha_src, alpha, start, (hipStream_t)stream));
+    return IRM_OK;
+}
+
+int irm_fit_alpha(irm_ctx* c, const float* traj, int32_t B, float* alpha_out) {
+    if (!c || !traj || !alpha_out) return fail(IRM_EINVAL, "irm_fit_alpha: null argument");
+    if (B < 0) return fail(IRM_EINVAL, "irm_fit_alpha: negative batch");
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    const size_t nd = (size_t)B * c->N * c->D;
+    Stage st{c};
+    const size_t o_q = st.take(nd * 4), o_a = st.take(nd * 4);
+    if (ensure_io(c, st.off)) return IRM_ENOMEM;
+    char* d = st.base();
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d + o_q, traj, nd * 4, hipMemcpyHostToDevice, s));
+    const int rc = irm_fit_alpha_dev(c, (const float*)(d + o_q), B, (float*)(d + o_a), s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(alpha_out, d + o_a, nd * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return IRM_OK;
+}
+
+int irm_transfer_alpha(irm_ctx* c, const float* alpha_src, int32_t B, float* alpha_out, float* start_out) {
+    if (!c || !alpha_src || !alpha_out) return fail(IRM_EINVAL, "irm_transfer_alpha: null argument");
+    if (c->xfer_src == 0) return fail(IRM_EINVAL, "irm_transfer_alpha: no transfer set (irm_set_transfer)");
+    if (B < 0) return fail(IRM_EINVAL, "irm_transfer_alpha: negative batch");
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    const size_t ns = (size_t)B * c->xfer_src * c->D, nd = (size_t)B * c->N * c->D, sd = (size_t)B * c->D;
+    Stage st{c};
+    const size_t o_s = st.take(ns * 4), o_a = st.take(nd * 4), o_q = st.take(sd * 4);
+    if (ensure_io(c, st.off)) return IRM_ENOMEM;
+    char* d = st.base();
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d + o_s, alpha_src, ns * 4, hipMemcpyHostToDevice, s));
+    const int rc = irm_transfer_alpha_dev(c, (const float*)(d + o_s), B, (float*)(d + o_a),
+                                          start_out ? (float*)(d + o_q) : nullptr, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(alpha_out, d + o_a, nd * 4, hipMemcpyDeviceToHost, s));
+    if (start_out) HIP_TRY(hipMemcpyAsync(start_out, d + o_q, sd * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return IRM_OK;
 }

@@ -343,5 +343,11 @@ hipError_t launch_cost_vg(const KParams& p, const float* f, float* cv, float* cg
 hipError_t launch_eval_any(const KParams& p, const float* mT, int M, float* out, hipStream_t s);
 hipError_t launch_dense_check(const KParams& p, const float* kqT, const float* dkqT, int M, irm_dense_report* rep,
                               float* cost, hipStream_t s);
+// irm_fit.hip — fitting and re-timing.  wT / tT: the fit / transfer operator on the device in fp64, transposed
+// ([source row m][waypoint n], n_src × N; W is N × N); kq0: the fp32 query row of the source grid at t0 (n_src);
+// p.B problems of p.N waypoints.  start_out nullable.
+hipError_t launch_fit_alpha(const KParams& p, const double* wT, const float* traj, float* alpha_out, hipStream_t s);
+hipError_t launch_transfer_alpha(const KParams& p, const double* tT, int n_src, const float* kq0, const float* alpha_src,
+                                 float* alpha_out, float* start_out, hipStream_t s);
 
 }  // namespace irm

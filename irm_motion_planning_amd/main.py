@@ -8,7 +8,8 @@ files trajectory_result.txt / trajectory_series.txt (np.savetxt defaults).
 
 Additive flags (no reference counterpart): --batch-size, --seed,
 --operator-rank, --device, --whole-robot-cost, --work-queue, --dense-check
-(which adds one stdout line and trajectory_result_dense.txt).
+(which adds one stdout line and trajectory_result_dense.txt) and
+--coarse-n-timesteps (coarse-to-fine: two stdout lines per optimize()).
 """
 import argparse
 import os
@@ -128,6 +129,10 @@ def build_parser():
                         help="After the report, evaluate the result on linspace(0, 1, M) — between the waypoints "
                              "the optimiser looked at — and print its obstacle cost, joint and velocity limits "
                              "there; writes trajectory_result_dense.txt (default: 0 = off)")
+    parser.add_argument('--coarse-n-timesteps', type=_sample_count, default=0, metavar='Nc',
+                        help="Coarse-to-fine: optimise on Nc support times first, carry that solution onto the "
+                             "--n-timesteps grid (transfer_alpha) and optimise from it; the output files are the "
+                             "fine stage's (default: 0 = off)")
     return parser
 
 
@@ -144,6 +149,28 @@ def parse_args(argv=None):
 
 
 DENSE_RESULT = "trajectory_result_dense.txt"
+
+
+def coarse_context(args):
+    """--coarse-n-timesteps Nc: a second context with the hyper-parameters of `args` on Nc support times."""
+    import copy
+
+    from .context import Context
+    from .params import params_from_args
+    ca = copy.copy(args)
+    ca.n_timesteps = args.coarse_n_timesteps
+    knobs = {k: getattr(args, k) for k in ("operator_rank", "device") if hasattr(args, k)}
+    return Context(params_from_args(ca, record_series=0, **knobs))
+
+
+def print_stages(stages):
+    """Both stages' statistics of a coarse-to-fine optimize(), one line each (sums over the batch)."""
+    for name in ("coarse", "fine"):
+        st = {k: np.atleast_1d(v) for k, v in stages[name]["stats"].items()}
+        print(name, "stage, N =", stages[name]["n_timesteps"], ": inner iterations", int(np.sum(st["inner_iterations"])),
+              ", outer iterations", int(np.sum(st["outer_iterations"])), ", gradient evaluations",
+              int(np.sum(st["grad_evals"])), ", constraint fulfiled", int(np.sum(st["constraints_ok"])), "of",
+              len(st["constraints_ok"]), ", final loss mean", float(np.mean(st["final_loss"])))
 
 
 def dense_report(context, alpha, obstacles, M):
@@ -192,12 +219,16 @@ def run_batch(optimizer, args):
         n_obs = int(np.asarray(env.obstacles).reshape(-1, 2).shape[0])
         if ctx.work_queue_groups(hi - lo, n_obs, args.extended_vis) == 0 and rank == 0:
             print("work queue", wq, "ignored: this launch runs one workgroup per group of problems")
+    coarse = coarse_context(args) if getattr(args, "coarse_n_timesteps", 0) > 0 else None
     runtimes = []
     res = None
     for _ in range(args.n_measurements):
         st = time.time()
         for _ in range(args.n_times):
-            res = optimizer.optimize_batch(start[lo:hi], goal[lo:hi], env.obstacles, series=args.extended_vis)
+            if coarse is not None:  # this process's problems (single GPU, or this rank's shard)
+                res = optimizer.coarse_to_fine(coarse, start[lo:hi], goal[lo:hi], env.obstacles, series=args.extended_vis)
+            else:
+                res = optimizer.optimize_batch(start[lo:hi], goal[lo:hi], env.obstacles, series=args.extended_vis)
         et = time.time()
         if world > 1:
             et = st + distributed.reduce_timing(et - st, 0, dev)[0]
@@ -206,6 +237,8 @@ def run_batch(optimizer, args):
             print("took", 1000 * (et - st) / args.n_times, "ms")
     if args.n_measurements > 1 and rank == 0:
         print("runtimes in ms: mean", np.mean(runtimes), "stddev", np.std(runtimes))
+    if coarse is not None and rank == 0:
+        print_stages(optimizer.last_stages)
     alpha, traj, stats = res[:3]
     series = res[3] if args.extended_vis else None
     if world > 1:
@@ -272,13 +305,23 @@ def main(argv=None):
     if args.batch_size > 1:
         return run_batch(optimizer, args)
 
+    coarse = coarse_context(args) if args.coarse_n_timesteps > 0 else None
+
+    def coarse_to_fine():
+        """optimizer.optimize() through the coarse stage: α, or (α, series) with --extended-vis."""
+        env = optimizer.env
+        res = optimizer.coarse_to_fine(coarse, env.start_config, env.goal_config, series=args.extended_vis)
+        if args.extended_vis:
+            return res[0][0], [np.array(f) for f in res[3][0][: int(res[2]["series_len"][0])]]
+        return res[0][0]
+
     def multiple_optimizations():
         runtimes = []
         result = None
         for _ in range(args.n_measurements):
             st = time.time()
             for _ in range(args.n_times):
-                result = optimizer.optimize()
+                result = optimizer.optimize() if coarse is None else coarse_to_fine()
             et = time.time()
             runtimes.append(1000 * (et - st) / args.n_times)
             print("took", 1000 * (et - st) / args.n_times, "ms")
@@ -290,6 +333,8 @@ def main(argv=None):
         result_alpha, p = multiple_optimizations()
     else:
         result_alpha = multiple_optimizations()
+    if coarse is not None:
+        print_stages(optimizer.last_stages)
     if args.profiling:
         for k, v in optimizer.last_profile.items():
             print("profile", k, v)

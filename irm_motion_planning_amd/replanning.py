@@ -13,7 +13,10 @@ straight line of initTrajectory (optimizer_BLS.py:57-62).
 * with warm_start the next plan starts from the previous plan's α, which never
   leaves HBM (α_out of call k is α0 of call k+1, double-buffered);
 * each call is one optimiser launch (k_lean / k_optimize) through irm_optimize_batch_dev on the
-  caller's stream (torch provides device memory and the stream).
+  caller's stream (torch provides device memory and the stream);
+* advance(tau) re-times the remaining motion of the latest plan onto [0, 1] on the device and makes the
+  plan's configuration at tau the new start (irm_transfer_alpha_dev), so a robot that has executed part
+  of its plan warm-starts the next one from where it is.
 
 The first call, or warm_start=False, is exactly Optimizer.optimize() for the batch.
 A warm-started call equals irm_optimize_batch with alpha0 = the previous α_out bit for
@@ -48,6 +51,7 @@ class Replanner:
         self.cur = 0          # index of the buffer holding the latest α
         self.planned = False  # is there a previous plan to warm-start from?
         self.calls = 0
+        self._tau = None      # the tau of the transfer operator the context holds (advance)
 
     def _put(self, dst, x, shape):
         x = np.array(np.broadcast_to(np.asarray(x, np.float32), shape))  # writable copy
@@ -89,6 +93,29 @@ class Replanner:
         out = {name: st[:, i].copy() for i, name in enumerate(STATS_FIELDS)}
         out["final_loss"] = st[:, STATS_FIELDS.index("final_loss")].view(np.float32).copy()
         return out
+
+    def advance(self, tau, stream=None):
+        """Receding horizon: the robot has executed the first `tau` (0 < tau < 1) of the latest plan.
+
+        The rest of that plan, re-timed onto [0, 1], becomes the α that the next
+        plan(obstacles, warm_start=True) starts from, and the plan's configuration at tau becomes
+        self.start — where the robot now is.  One irm_transfer_alpha_dev launch from the current α buffer
+        into the other one (the buffers flip; α never leaves HBM), enqueue-only on `stream`.  The
+        transfer operator is rebuilt only when tau changes.
+
+        The remaining duration is stretched to unit time: velocities in the new parametrisation are
+        (1 − tau) times the old ones (a plan that kept the velocity limit keeps it).  trajectory() and
+        the statistics still describe the plan before the advance until the next plan()."""
+        if not self.planned:
+            raise IrmError("advance() needs a plan: call plan() first")
+        tau = float(tau)
+        if self._tau != tau:
+            self.context.set_transfer(self.N, t0=tau, t1=1.0)  # IrmError unless tau is finite and < 1
+            self._tau = tau
+        s = stream if stream is not None else self.torch.cuda.current_stream(self.device)
+        a_in, a_out = self._alpha[self.cur], self._alpha[self.cur ^ 1]
+        self.context.transfer_alpha_dev(a_in.data_ptr(), self.B, a_out.data_ptr(), self.start.data_ptr(), s.cuda_stream)
+        self.cur ^= 1
 
     def alpha(self):
         """The latest plan's α (B×N×D, device tensor)."""

@@ -7,6 +7,7 @@ meaning; every method runs a HIP kernel through the C ABI:
   evaluate                    trajectory.py:63-65   irm_evaluate
   eval_any                    trajectory.py:68-70   irm_set_eval_times + irm_eval_any
   initTrajectory              trajectory.py:73-78   irm_init_alpha
+  fit                         (none)                irm_fit_alpha
   compute_trajectory_cost     trajectory.py:271-281 irm_eval_cost
   compute_trajectory_cost_g   trajectory.py:284-297 irm_eval_cost_grad
   constraintsFulfilled        trajectory.py:129-137 irm_constraints
@@ -84,6 +85,13 @@ class Trajectory:
 
     def initTrajectory(self, start_config, goal_config):
         return self.context.init_alpha(start_config, goal_config)
+
+    def fit(self, waypoints):
+        """α for given joint waypoints ((B×)N×D on self.t) — the other way into the optimiser next to
+        initTrajectory: a recorded path or another planner's output (irm_fit_alpha, a ridge fit:
+        evaluate(fit(q), self.km, self.jac) reproduces a smooth q to ~1e-4).  No reference
+        counterpart."""
+        return self.context.fit_alpha(waypoints)
 
     # ----------------------------------------------------------------- costs
     def compute_trajectory_cost(self, alpha, obstacles, start_config, goal_config, lambda_sg_constraint,

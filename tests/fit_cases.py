@@ -1,0 +1,266 @@
+"""Shared by tests/test_fit_host.py (CPU) and tests/test_gpu_fit.py (GPU): the cases, their seeded inputs and the
+numpy fp64 restatement of fit_alpha / transfer_alpha (DESIGN.md §2 "Fitting and re-timing"), built from the
+library's own operators (irm_fit_operator, irm_query_matrices).  Nothing here needs a device: the inputs come from
+the CPU oracle's initTrajectory, so the tolerances the CPU suite records are those of the GPU suite's inputs."""
+import functools
+
+import numpy as np
+
+from conftest import oracle_for
+
+f32, f64 = np.float32, np.float64
+
+# (n_src, N, D, B, t0); t1 = 1 throughout.  N off the wave (50) and off the operator prefetch batch of 4 (50),
+# partial workgroups (B = 5, 1, 2 with 4 problems per workgroup at D = 3, 2 at D = 7), n_src smaller and larger
+# than N, a re-timed pair, and the size limit (512: two chunks of 256 lanes).
+CASES = [
+    (50, 50, 3, 5, 0.0),
+    (32, 64, 3, 5, 0.0),
+    (64, 128, 7, 5, 0.0),
+    (128, 50, 3, 1, 0.0),
+    (128, 128, 3, 5, 0.1),
+    (128, 128, 3, 5, 0.3),
+    (512, 512, 3, 2, 0.0),
+]
+T1 = 1.0
+
+
+def case_id(case):
+    n_src, N, D, B, t0 = case
+    return f"{n_src}to{N}-D{D}-B{B}-t{t0}"
+
+
+# Reproduction error of the numpy fp64 restatement on the inputs below (max over batch, waypoints and joints):
+# the operator applied in fp64, α rounded to fp32 once, then K·α·J (positions) and dK·α·J (velocities) in fp64,
+# against the source trajectory Kx·α_src·J and (t1 − t0)·dKx·α_src·J at the mapped times in fp64.
+# tests/test_fit_host.py::test_recorded_reproduction_errors recomputes every number here on the CPU and requires
+# the committed value to match it to 1 %; the GPU tests allow 2× the number of their case.  Recorded with
+# numpy 2.x / OpenBLAS on x86-64 (the fp64 products' summation order moves the numbers in the 4th digit at most).
+TRANSFER_ERR = {
+    # case id: (positions, velocities)
+    "50to50-D3-B5-t0.0": (1.400e-4, 3.249e-2),
+    "32to64-D3-B5-t0.0": (2.056e-4, 1.943e-2),
+    "64to128-D7-B5-t0.0": (3.269e-4, 2.163e-2),
+    "128to50-D3-B1-t0.0": (1.387e-4, 3.738e-2),
+    "128to128-D3-B5-t0.1": (9.487e-5, 2.937e-2),
+    "128to128-D3-B5-t0.3": (9.378e-5, 3.624e-2),
+    # N = 512: the fit's max|α| is 1.7e4 here (1e2 to 4e2 above), and its fp32 rounding alone moves K·α·J by ~1e-2
+    "512to512-D3-B2-t0.0": (1.815e-2, 3.315e-1),
+}
+
+# The same for fit_alpha on the (N, D) grids of CASES: waypoints Q = fp32(K·α·J) of the inputs (the bumps) and of
+# the plain initTrajectory line, α = fp32(W·(Q·Jinv)) in fp64, max|K·α·J − Q|.
+FIT_ERR = {
+    # (N, D): (bumps, line)
+    (50, 3): (1.411e-4, 1.400e-4),
+    (64, 3): (2.502e-4, 2.581e-4),
+    (128, 7): (1.348e-4, 1.402e-4),
+    (128, 3): (1.351e-4, 1.196e-4),
+    (512, 3): (1.765e-2, 1.776e-2),
+}
+
+
+def shape_argv(N, D):
+    argv = ["--n-timesteps", str(N), "--n-joints", str(D)]
+    if D != 3:
+        argv += ["--link-length"] + [str(3.0 / D)] * D
+    return argv
+
+
+def query(n, t_eval, var=0.1):
+    """Kq, dKq (M×n, fp32) of n support times at t_eval, as the library builds them."""
+    from irm_motion_planning_amd._abi import c_float_p, check, load_library
+    t = np.ascontiguousarray(t_eval, f32)
+    kq = np.zeros((t.shape[0], n), f32)
+    dkq = np.zeros_like(kq)
+    check(load_library().irm_query_matrices(n, var, t.ctypes.data_as(c_float_p), t.shape[0],
+                                            kq.ctypes.data_as(c_float_p), dkq.ctypes.data_as(c_float_p)))
+    return kq, dkq
+
+
+def support(n):
+    return np.linspace(0, 1, n, dtype=f32)
+
+
+def mapped_times(N, t0, t1=T1):
+    """s_i = t0 + (t1 − t0)·t_i in fp32, as irm_set_transfer forms them."""
+    return (f32(t0) + (f32(t1) - f32(t0)) * support(N)).astype(f32)
+
+
+@functools.lru_cache(maxsize=None)
+def grid(N, D):
+    """t, K, dK, J of the (N, D) configuration (fp32, from the CPU oracle — the library's are the same bits,
+    tests/test_gpu_reference.py)."""
+    return oracle_for(*shape_argv(N, D)).kernel_matrices()
+
+
+@functools.lru_cache(maxsize=None)
+def line_alpha(N, D, B):
+    """initTrajectory of B seeded start/goal pairs on the N grid (the CPU oracle's: fp32 LU like the library's)."""
+    rng = np.random.default_rng(1000 * N + D)
+    s = rng.uniform(-0.5, 0.5, (B, D)).astype(f32)
+    g = rng.uniform(0.2, 1.6, (B, D)).astype(f32)
+    o = oracle_for(*shape_argv(N, D))
+    return np.stack([o.init_alpha(s[b], g[b]) for b in range(B)])
+
+
+@functools.lru_cache(maxsize=None)
+def bump_alpha(N, D, B):
+    """The smooth inputs: the line's α plus two kernel bumps of amplitude ≤ 0.5 at support indices N/3 and 2N/3."""
+    a = line_alpha(N, D, B).copy()
+    rng = np.random.default_rng(7000 * N + D)
+    a[:, N // 3, :] += rng.uniform(-0.5, 0.5, (B, D)).astype(f32)
+    a[:, (2 * N) // 3, :] += rng.uniform(-0.5, 0.5, (B, D)).astype(f32)
+    return a
+
+
+# ------------------------------------------------------------------ the library's fp32 J⁻¹, restated
+def _getrf2(A, ipiv):
+    """irm_host.cpp getrf2_f32 on a float32 view (recursive LAPACK order, every operation rounded to fp32)."""
+    m, n = A.shape
+    if n == 1:
+        p = 0
+        for i in range(1, m):
+            if abs(A[i, 0]) > abs(A[p, 0]):
+                p = i
+        ipiv[0] = p
+        if p != 0:
+            A[0, 0], A[p, 0] = A[p, 0], A[0, 0]
+        if A[0, 0] != 0:
+            r = f32(1) / A[0, 0]
+            for i in range(1, m):
+                A[i, 0] = A[i, 0] * r
+        return
+    n1 = min(m, n) // 2
+    _getrf2(A[:, :n1], ipiv[:n1])
+    for i in range(n1):
+        if ipiv[i] != i:
+            for j in range(n1, n):
+                A[i, j], A[ipiv[i], j] = A[ipiv[i], j], A[i, j]
+    for i in range(1, n1):
+        for k in range(i):
+            l = A[i, k]
+            for j in range(n1, n):
+                A[i, j] = A[i, j] - l * A[k, j]
+    for i in range(n1, m):
+        for j in range(n1, n):
+            s = f32(0)
+            for k in range(n1):
+                s = s + A[i, k] * A[k, j]
+            A[i, j] = A[i, j] - s
+    _getrf2(A[n1:, n1:], ipiv[n1:])
+    for i in range(n1, min(m, n)):
+        ipiv[i] += n1
+        if ipiv[i] != i:
+            for j in range(n1):
+                A[i, j], A[ipiv[i], j] = A[ipiv[i], j], A[i, j]
+
+
+def jinv32(J):
+    """The context's fp32 J⁻¹: lu_solve_f32(J, I) of irm_host.cpp, operation by operation."""
+    D = J.shape[0]
+    A = np.array(J, f32)
+    X = np.eye(D, dtype=f32)
+    ipiv = np.zeros(D, np.int64)
+    _getrf2(A, ipiv)
+    for i in range(D):
+        if ipiv[i] != i:
+            X[[i, ipiv[i]]] = X[[ipiv[i], i]]
+    for j in range(D):
+        for i in range(1, D):
+            s = X[i, j]
+            for k in range(i):
+                s = s - A[i, k] * X[k, j]
+            X[i, j] = s
+        for i in range(D - 1, -1, -1):
+            s = X[i, j]
+            for k in range(i + 1, D):
+                s = s - A[i, k] * X[k, j]
+            X[i, j] = s / A[i, i]
+    return X
+
+
+# ------------------------------------------------------------------ restatements
+def chain(M, X):
+    """Σ_m M[:, m]·X[m] in fp64 in the order m = 0, 1, …: with fp32 inputs every product is exact, so this is an
+    FMA chain bit for bit (tests/test_gpu_dense.py restate)."""
+    acc = np.zeros((M.shape[0], X.shape[1]), f64)
+    for m in range(X.shape[0]):
+        acc += M[:, m, None].astype(f64) * X[m].astype(f64)
+    return acc
+
+
+def evaluate32(M, alpha, J):
+    """The device's evaluation fp32(fp32(M·α)·J) (irm_evaluate / irm_eval_any), to the bit."""
+    return chain(chain(M, alpha).astype(f32), J).astype(f32)
+
+
+def operator(N, n_src=0, t0=0.0, t1=T1):
+    from irm_motion_planning_amd.context import fit_operator
+    return fit_operator(N, 0.1, n_src=n_src, t0=t0, t1=t1)
+
+
+def apply64(Op, X):
+    """α_ref = Op·X in fp64 and the bound of the device's result against it: half an fp32 ulp of α_ref for the
+    final rounding plus n·2⁻⁵²·Σ_m|Op_nm·x_m| — two fp64 sums of the same n products, in any order, with or
+    without fused multiply-adds, differ by at most 2·n·2⁻⁵³ times the sum of the products' magnitudes."""
+    ref = Op @ X
+    mag = np.abs(Op) @ np.abs(X)
+    ulp = np.spacing(np.abs(ref).astype(f32)).astype(f64)
+    return ref, ulp / 2 + Op.shape[1] * 2.0 ** -52 * mag
+
+
+def fit_sources(Q, Jinv):
+    """X[m][k] = Σ_d Q[m][d]·Jinv[d][k] as the kernel stages it (an fp64 FMA chain over d; exact products)."""
+    return chain(Q, Jinv)
+
+
+@functools.lru_cache(maxsize=None)
+def transfer_restatement(case):
+    """Per problem: α_ref (fp64), its bound, and the reproduction errors of fp32(α_ref)."""
+    n_src, N, D, B, t0 = case
+    a_src = bump_alpha(n_src, D, B)
+    _, K, dK, J = grid(N, D)
+    T = operator(N, n_src, t0)
+    s = mapped_times(N, t0)
+    kx, dkx = query(n_src, s)
+    out = {"alpha_src": a_src, "T": T, "s": s, "ref": [], "bound": [], "pos_err": 0.0, "vel_err": 0.0}
+    J64, scale = J.astype(f64), float(f32(T1) - f32(t0))
+    for b in range(B):
+        ref, bound = apply64(T, a_src[b].astype(f64))
+        out["ref"].append(ref)
+        out["bound"].append(bound)
+        a = ref.astype(f32).astype(f64)
+        src = a_src[b].astype(f64)
+        out["pos_err"] = max(out["pos_err"], float(np.abs(K.astype(f64) @ a @ J64 - kx.astype(f64) @ src @ J64).max()))
+        out["vel_err"] = max(out["vel_err"],
+                             float(np.abs(dK.astype(f64) @ a @ J64 - scale * (dkx.astype(f64) @ src @ J64)).max()))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def fit_restatement(N, D, B, kind):
+    """kind "bumps" / "line": waypoints Q (what irm_evaluate returns for the inputs), α_ref, bound, error."""
+    alpha = bump_alpha(N, D, B) if kind == "bumps" else line_alpha(N, D, B)
+    _, K, _, J = grid(N, D)
+    W = operator(N)
+    Jinv = jinv32(J)
+    out = {"Q": [], "ref": [], "bound": [], "err": 0.0}
+    for b in range(B):
+        Q = evaluate32(K, alpha[b], J)
+        ref, bound = apply64(W, fit_sources(Q, Jinv))
+        out["Q"].append(Q)
+        out["ref"].append(ref)
+        out["bound"].append(bound)
+        a = ref.astype(f32).astype(f64)
+        out["err"] = max(out["err"], float(np.abs(K.astype(f64) @ a @ J.astype(f64) - Q.astype(f64)).max()))
+    out["Q"] = np.stack(out["Q"])
+    return out
+
+
+def fit_grids():
+    """The (N, D, B) grids the fit tests run on: the targets of CASES."""
+    seen = {}
+    for _, N, D, B, _ in CASES:
+        seen.setdefault((N, D), B)
+    return [(N, D, B) for (N, D), B in seen.items()]
