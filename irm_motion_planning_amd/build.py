@@ -5,8 +5,11 @@
 The optimiser templates (csrc/irm_kernels_impl.hpp) are instantiated in one
 object per problem shape (csrc/irm_opt_inst.hip compiled with IRM_INST_*), so
 the objects build in parallel; the host-API kernels and dispatch
-(irm_kernels.hip) and the C ABI (irm_host.cpp) are two more objects.  The .so
-lands next to this file so that it travels with the repository snapshot to the
+(irm_kernels.hip), the C ABI (irm_host.cpp) and the device-free operator build
+behind irm_ctx_create (irm_operator.cpp: build_operators, fill_kparams,
+choose_shape; no HIP header) are three more objects.  irm_layout.hpp is what
+host and kernels share without a HIP type (KParams, fragment and LDS layouts),
+irm_kernels.hpp adds the launchers.  The .so lands next to this file so that it travels with the repository snapshot to the
 GPU box (it is git-ignored, not gpurun-ignored); objects stay in _obj/.
 """
 import glob
@@ -20,7 +23,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 OUT = os.path.join(HERE, "libirm_hip.so")
-HEADERS = [os.path.join(CSRC, h) for h in ("irm_kernels.hpp", "irm_kernels_impl.hpp")] + \
+HEADERS = [os.path.join(CSRC, h) for h in ("irm_kernels.hpp", "irm_kernels_impl.hpp", "irm_layout.hpp",
+                                           "irm_operator.hpp")] + \
     [os.path.join(HERE, "..", "include", "irm.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
@@ -96,6 +100,8 @@ def add_variant(name, flags):
 def _units():
     """(object name, source, extra flags) of every compilation unit, before the build id."""
     u = [("irm_kernels", "irm_kernels.hip", []), ("irm_host", "irm_host.cpp", [])]
+    # the operator build of irm_ctx_create: host code only, the common CFLAGS (-ffp-contract=off decides its roundings)
+    u += [("irm_operator", "irm_operator.cpp", [])]
     # (DynShape units keep the default scheduler: with iterative-ILP the D = 5 register-resident
     # variant, which spills heavily, left the exact-iteration band — tests/test_gpu_parity.py::
     # test_generic_shapes_match_reference_iteration[64-5] — so it is not used there)

@@ -116,7 +116,7 @@ def bump_alpha(N, D, B):
 
 # ------------------------------------------------------------------ the library's fp32 J⁻¹, restated
 def _getrf2(A, ipiv):
-    """irm_host.cpp getrf2_f32 on a float32 view (recursive LAPACK order, every operation rounded to fp32)."""
+    """irm_operator.cpp getrf2_f32 on a float32 view (recursive LAPACK order, every operation rounded to fp32)."""
     m, n = A.shape
     if n == 1:
         p = 0
@@ -157,7 +157,7 @@ def _getrf2(A, ipiv):
 
 
 def jinv32(J):
-    """The context's fp32 J⁻¹: lu_solve_f32(J, I) of irm_host.cpp, operation by operation."""
+    """The context's fp32 J⁻¹: lu_solve_f32(J, I) of irm_operator.cpp, operation by operation."""
     D = J.shape[0]
     A = np.array(J, f32)
     X = np.eye(D, dtype=f32)

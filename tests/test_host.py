@@ -44,7 +44,7 @@ def operator(N):
     w, V = np.linalg.eigh(L.T @ L)
     w, V = w[::-1], V[:, ::-1]
     R = 16
-    while R < N and w[R] / w[0] >= 1e-12:  # irm_host.cpp auto rank: σ_R²/σ_0² < 1e-12
+    while R < N and w[R] / w[0] >= 1e-12:  # irm_operator.cpp auto rank: σ_R²/σ_0² < 1e-12
         R += 16
     R = min(R, N)
     return L, L @ V[:, :R], R, K.astype(np.float64), dK.astype(np.float64), J.astype(np.float64)
