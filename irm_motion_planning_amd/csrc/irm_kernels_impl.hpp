@@ -2504,8 +2504,33 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     // (the GD dual loop with the same prefetch: 4.33 -> 4.47 ms, 242 VGPRs there; not used)
     constexpr bool kPre1 = GD1 && FULL && kFix1;
     constexpr bool kPreW = kPre1 && RV;
+    // C3's kernel (N = 128 in 512-thread workgroups): the round's LDS reads issued in the order of their use —
+    // the round top and the decision, below.  Issue order only: same loads, same MFMAs, same order per chain
+    // (bit-identical, tools/sched_check.py).  Alternating 300-step bench runs against the parent build: stage
+    // 1's order alone −0.6 %, the G words alone −0.7 %, both −1.6 % (profiles/gd1_top_ab.txt); the z unit's
+    // e' quads read at the round top as well measured +0.8 % alone and is not done
+    constexpr bool kTopC3 = kPreW && D <= 3 && WPL == 1 && MAXT > 256 && WPTL > 1 && kLatS;
+    constexpr bool kS1Ord = kTopC3;  // flag word first, stage 1's operands in use order
+    constexpr bool kGFin = kTopC3;   // the α update's G words read with finalize's records
     auto stage1_load = [&](f32x4 (&bv)[KQU1], f32x4 (&bw)[KQU1], float& bep) {
         const float* xl = X + cl * ldx + r4x;
+        if constexpr (kS1Ord) {
+            // (has1 waves) the endpoint word, then the position quads in the order stage 1's chains consume
+            // them, then the velocity quads: LDS returns in order, so each MFMA group waits for its own quad
+            bep = smem[epoff];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < KQU1; ++i) {
+                bv[i] = *reinterpret_cast<const f32x4*>(xl + (kq0 + i) * 16);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int i = 0; i < KQU1; ++i) {
+                bw[i] = *reinterpret_cast<const f32x4*>(xl + (KQa + kq0 + i) * 16);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            return;
+        }
         if (has1) {  // wave-uniform
 #pragma unroll
             for (int i = 0; i < KQU1; ++i) {
@@ -3473,8 +3498,24 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         float pre1e = 0.f;  // read only on the endpoint waves (hasep)
         // (the flag word read before the operand batch, so the branch need not wait for the batch: C3 even
         // to 2 % slower, not kept)
-        if constexpr (kPre1) stage1_load(pre1, pre1w, pre1e);
-        const unsigned fl = fw[par];
+        unsigned flw = 0u;
+        if constexpr (kS1Ord) {
+            // C3's kernel: the flag word first, then the stage-1 waves' operands in the order of their use, all
+            // in one LDS queue.  The flag becomes a scalar inside each wave class's own block, so its wait
+            // counts that block's later reads (lgkmcnt(9) on the stage-1 waves) instead of draining them,
+            // and stage 1's MFMA groups each wait for their own quad.  X and the endpoint copy were written
+            // before the round-end barrier
+            const unsigned flv = fw[par];
+            __builtin_amdgcn_sched_barrier(0);
+            if (has1) {  // wave-uniform
+                stage1_load(pre1, pre1w, pre1e);
+                asm volatile("v_readfirstlane_b32 %0, %1 ; flag word, stage-1 waves" : "=s"(flw) : "v"(flv));
+            } else {
+                asm volatile("v_readfirstlane_b32 %0, %1 ; flag word, other waves" : "=s"(flw) : "v"(flv));
+            }
+        }
+        if constexpr (kPre1 && !kS1Ord) stage1_load(pre1, pre1w, pre1e);
+        const unsigned fl = kS1Ord ? flw : fw[par];
         if constexpr (GD1) {
             if ((fl & 0x7FFFFFFFu) == 0u) break;  // every trajectory of the block is done
         } else {
@@ -3483,7 +3524,10 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         const bool dense = (fl >> 31) != 0u;
         const bool dirr = GD1 || ((fl >> 28) & 1u);  // some trajectory needs a direction this round
         const bool rsy = !GD1 && ((fl >> 29) & 1u);  // some trajectory ends an inner loop this round
-        if (tid == 0) fw[par ^ 1] = 0u;
+        // (kS1Ord: cleared behind stage 1 — here the store's wait drained wave 0's operand batch)
+        if constexpr (!kS1Ord) {
+            if (tid == 0) fw[par ^ 1] = 0u;
+        }
         if constexpr (QUE) {
             // the index this slot's first wave took at the end of the previous round (its record's spare word):
             // a problem to load this round, or past the batch — the slot stays done
@@ -3583,6 +3627,11 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                 } else {
                     stage1(dense, pre1, pre1w, pre1e);
                     stage1z(zpre);
+                    // the next round's flag word: last read at the previous round's top, next set by this
+                    // round's decisions (two barriers on either side)
+                    if constexpr (kS1Ord) {
+                        if (tid == 0) fw[par ^ 1] = 0u;
+                    }
                 }
                 IRM_STAMP(1);
                 __syncthreads();
@@ -3857,6 +3906,15 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         if (ev && !helper) {
             const bool rs = !GD1 && phase == LP_RESYNC;
             const float lsg_e = rs ? lsg * P.lci : lsg;
+            // (kGFin) the lane's G words of the α update read in one batch with finalize's records (glate_tiles
+            // wrote Gb before the evaluation's barrier; finalize's reads stay behind its scheduling barrier):
+            // the accepted step waits on no LDS read of its own; a rejected step leaves them unused
+            float Gf[kGFin ? WPL : 1][D];
+            if constexpr (kGFin) {
+                static_assert(kGLate && !kGPre, "G is read after the evaluation's barrier");
+#pragma unroll
+                for (int j = 0; j < WPL; ++j) grad_alpha(j, Gf[j], t);
+            }
             const Fin f = finalize(lsg_e, t);
             IRM_STAMP(9);
             bool bfar = false, to_end = false, accept = false, snap = false, more = false;
@@ -4013,6 +4071,9 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                     if constexpr (kGPre) {
 #pragma unroll
                         for (int k = 0; k < D; ++k) G[k] = Gp[j][k];
+                    } else if constexpr (kGFin) {
+#pragma unroll
+                        for (int k = 0; k < D; ++k) G[k] = Gf[j][k];
                     } else {
                         grad_alpha(j, G, t);
                     }
