@@ -3491,7 +3491,153 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
 #ifdef IRM_X_PRIO_RESTORE
     bool hm_prev = false;  // (kHelp) the previous round was a helper round: its priorities are still set
 #endif
-    for (int par = 0;; par ^= 1) {
+    // ---- the all-live loop (C3's kernel, kTopC3).  A workgroup whose every slot holds a problem runs its
+    // rounds here up to and including the first in which one of its trajectories stops (a rejected step, or
+    // max_inner reached); the loop below takes over from there, and runs a ragged batch's last, partial
+    // workgroup from the start.  Same stages, LDS layout, MFMA chains and per-lane arithmetic as a round of
+    // the loop below with every trajectory stepping (bit-identical, tests/test_gpu_gd1_fastpath.py); what the
+    // round no longer carries: the done / stepping tests and the waypoint-state copies behind them, the
+    // wave-role tests inside the stages (stage-1 waves and z waves take one branch each), the per-round
+    // counters (one round count per wave, added to the statistics at the exit), the flag word's decoding
+    // beyond "all eight wave bits set" (a stopped trajectory's waves leave theirs unset: the stop bit) and
+    // the three compares of b' for the dense bit (the evaluation's velocity masks zvm decide it: b' = k_vel·zvm
+    // away from the endpoints, and a dense round where b' is zero adds exact zeros).
+    // The hand-over is the flag word itself: the loop below reads the word this loop declined.
+    int par0 = 0;
+    if constexpr (kTopC3) {
+        constexpr int kW1 = (S::RP / 16) * S::NSPLIT;  // the stage-1 waves; the z unit's are all the others
+        static_assert(kW1 + kZS == MAXT / 64 && kZFix && !kZPre && kGLate && kGFin && kLatF && kAllLive && kLeanKeep<D>,
+                      "the all-live loop is written for C3's kernel");
+        if (ntb == kSlots) {  // workgroup-uniform: every slot holds a problem
+            constexpr unsigned kAllW = (1u << (MAXT / 64)) - 1u;
+            const unsigned wbit = 1u << wave;
+            const LeanW cw = lean_weights(P, ljl);
+            const f32x4 zpre[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};  // (kVReg: the z unit's fragments are in vtR)
+            float llr = P.llr;  // (held in a register: the decision does not wait for a kernel-argument load)
+            asm volatile("" : "+s"(llr));
+            int rnd = 0;       // accepted steps here (a gradient and a cost evaluation each)
+            bool rej = false;  // left through a rejected step (one more gradient and cost evaluation)
+            int par = 0;
+            for (;; par ^= 1) {
+                f32x4 pre1[KQU1], pre1w[KQU1];
+                float pre1e = 0.f;
+                unsigned fl = 0u;
+                const unsigned flv = fw[par];
+                __builtin_amdgcn_sched_barrier(0);
+                // one branch per wave role: the flag word, the exit test and the wave's stage-1 unit
+                // (somebody stopped — a wave bit is missing: the loop below reads this word again)
+                if (has1) {  // wave-uniform
+                    stage1_load(pre1, pre1w, pre1e);
+                    asm volatile("v_readfirstlane_b32 %0, %1 ; flag word, stage-1 waves (all-live)" : "=s"(fl) : "v"(flv));
+                    if ((fl & kAllW) != kAllW) break;
+                    IRM_STAMP(0);
+                    IRM_COUNT(13, (fl >> 31) != 0u);
+                    stage1((fl >> 31) != 0u, pre1, pre1w, pre1e);
+                    // the next round's flag word (as below), by wave 0 alone under a scalar branch: behind a lane
+                    // mask the store is issued, with no lane enabled, by the three other stage-1 waves as well
+                    if (wave == 0) fw[par ^ 1] = 0u;
+                } else {
+                    asm volatile("v_readfirstlane_b32 %0, %1 ; flag word, z waves (all-live)" : "=s"(fl) : "v"(flv));
+                    if ((fl & kAllW) != kAllW) break;
+                    stage1z(zpre);
+                }
+                IRM_STAMP(1);
+                __syncthreads();
+                IRM_STAMP(2);
+                stage2f(std::true_type{}, std::true_type{});
+                IRM_STAMP(3);
+                __syncthreads();
+                IRM_STAMP(4);
+                glate_tiles();
+                // update + evaluate: the waypoint state moves to the trial point (a rejected step ends the trajectory)
+                float q2[WPL][D], v2[WPL][D];
+                WP<D> w[WPL];
+                {
+                    float dt[D], dv[D];
+                    direction(0, dt, dv);
+#pragma unroll
+                    for (int k = 0; k < D; ++k) {
+                        const float tq = -(lr * dt[k]), tv = -(lr * dv[k]);
+                        q2[0][k] = fmaf(cfac, q[0][k], tq);
+                        v2[0][k] = fmaf(cfac, v[0][k], tv);
+                        asm volatile("" ::"v"(tq), "v"(tv), "v"(q2[0][k]), "v"(v2[0][k]));  // (three-address FMAs, as below)
+                    }
+                }
+                IRM_STAMP(5);
+#pragma unroll
+                for (int k = 0; k < D; ++k) {
+                    q[0][k] = q2[0][k];
+                    v[0][k] = v2[0][k];
+                }
+                evaluate(q2, v2, false, ljl, w);
+                IRM_STAMP(7);
+                __syncthreads();
+                IRM_STAMP(8);
+                // ---- decision
+                float Gf[D];
+                grad_alpha(0, Gf, t);
+                const Fin f = finalize(lsg, t);
+                IRM_STAMP(9);
+                if (loss - f.nl < llr) {
+                    // minimized: the step is discarded (optimizer_GD.py:87-90) and the trajectory ends with the α,
+                    // loss and step count it has.  Its waves leave from here, behind the round's end barrier;
+                    // their bits are missing in the next flag word, so every other wave leaves at the next top
+                    rej = true;
+                    par ^= 1;
+                    IRM_STAMP(11);
+                    __syncthreads();
+                    IRM_STAMP(12);
+                    break;
+                } else {
+                    loss = f.nl;
+                    float eo[D];
+#pragma unroll
+                    for (int k = 0; k < D; ++k) al[0][k] = alpha_step_gd2(al[0][k], cfac, lr, Gf[k], nilr, eo[k]);
+#pragma unroll
+                    for (int k = 0; k < D; ++k) Eb[(t * D + k) * lde + swz(nn[0], t * D + k)] = eo[k];
+                    if (rnd + 1 < P.max_inner) {  // (every round so far was a step: inner = rnd)
+                        // gradient inputs at the new point (grad_inputs), the dense bit from the velocity masks
+                        const int n = nn[0];
+                        float a[D], bb[D], ep[D];
+                        grad_waypoint_lean<D>(P, w[0], q2[0], v2[0], n == f.idx, epf[0] * lsg, cw, tg[0], a, bb);
+                        unsigned zb = 0u;
+#pragma unroll
+                        for (int k = 0; k < D; ++k) {
+                            float ma = 0.f, mb = 0.f;
+#pragma unroll
+                            for (int d = 0; d < D; ++d) {
+                                ma = fmaf(a[d], P.J[k * D + d], ma);
+                                mb = fmaf(bb[d], P.J[k * D + d], mb);
+                            }
+                            X[(t * D + k) * ldx + swz(n, t * D + k)] = ma;
+                            X[(t * D + k) * ldx + NK + swz(n, t * D + k)] = mb;
+                            zb |= __float_as_uint(w[0].zvm[k]);
+                            ep[k] = mb;
+                        }
+                        const bool bfar = (__ballot(zb != 0u) & ~endm[0]) != 0ull;
+                        if (epf[0] != 0.f) {  // the compact copy of the endpoint rows
+                            float* e = EPt + (n == 0 ? 0 : kEpS);
+#pragma unroll
+                            for (int k = 0; k < D; ++k) e[k] = ep[k];
+                        }
+                        if (lane == 0) atomicOr(&fw[par ^ 1], wbit | (bfar ? 1u << 31 : 0u));
+                    }
+                }
+                ++rnd;
+                IRM_STAMP(11);
+                __syncthreads();
+                IRM_STAMP(12);
+            }
+            // the loop below continues at this parity with the state it keeps per round
+            par0 = par;
+            st.grad_evals += rnd + (rej ? 1 : 0);
+            st.cost_evals += rnd + (rej ? 1 : 0);
+            st.inner_iterations += rnd;
+            inner += rnd;
+            if (rej || inner >= P.max_inner) done = true;
+        }
+    }
+    for (int par = par0;; par ^= 1) {
         f32x4 pre1[KQU1], pre1w[KQU1];
         f32x4 zpre[kZPre ? kKQZ : 1];
         zpre_load(zpre);

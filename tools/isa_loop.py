@@ -1,6 +1,6 @@
 """Instruction mix of a k_lean kernel's round loop from hipcc -S device assembly (static).
 
-    python tools/isa_loop.py /tmp/asm/fix3128.s '512, 1, true, 0' [--blocks]
+    python tools/isa_loop.py /tmp/asm/fix3128.s '512, 1, true, 0' [--blocks] [--loop N]
 
 The loop is the kernel's outermost loop with the most blocks (the rounds).  Its blocks are split into
 the main chain — the loop header up to the latch block that branches back to it, LLVM's placement of
@@ -53,6 +53,9 @@ for b in blocks:
     if b[1]:
         loops[b[1]].append(b)
 hdr = max(loops, key=lambda k: len(loops[k]))
+if "--loop" in sys.argv:  # the n-th of the kernel's large loops in program order (0: the all-live loop of C3's kernel)
+    big = [k for k in loops if len(loops[k]) >= 20]
+    hdr = big[int(sys.argv[sys.argv.index("--loop") + 1])]
 lb = loops[hdr]
 latch = max((i for i, b in enumerate(lb) if (".L" + hdr) in b[4]), default=len(lb) - 1)  # (fall-through back edge: the last block)
 hot = [b for i, b in enumerate(lb) if i <= latch and not b[2]]
