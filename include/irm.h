@@ -357,6 +357,51 @@ int irm_fit_alpha_dev(irm_ctx* ctx, const float* traj_dev, int32_t batch, float*
 int irm_transfer_alpha_dev(irm_ctx* ctx, const float* alpha_src_dev, int32_t batch, float* alpha_dev,
                            float* start_dev, void* stream);
 
+/* Moving obstacles: constant-velocity prediction inside a plan.  Every obstacle o has a velocity w_o
+ * (displacement per unit of plan time; the plan runs over t ∈ [0, 1]), and a waypoint at plan time τ sees
+ * obstacle o at
+ *   x = fmaf(τ, w_x, p_x),  y = fmaf(τ, w_y, p_y)         fp32, one fused multiply-add per coordinate
+ * From there the potential's arithmetic is the static one's (environment.py:46-58 as the kernels evaluate it).
+ * τ is the support time t[n] — the fp32 value irm_kernel_matrices returns — for the cost, the gradient and
+ * every round of the optimiser, and t_eval[i] for irm_dense_check_moving.  The obstacle moves with time, not
+ * with α: the gradient is the static formula with each waypoint's own obstacle positions, no new term; the
+ * max-cost term, the mean weighting and the whole-robot cost (every joint position of waypoint n sees the
+ * table at t[n]) compose unchanged.
+ * obstacle_velocity is fp32 with the shape and stride of `obstacles` (O×2 shared, or one table per problem
+ * at obstacle_stride).  NULL means the static call: the same dispatch and the same bits as the entry point
+ * without _moving.  An all-zero table gives the same kernel's static result to the bit (fmaf(τ, 0, p) = p).
+ * A moving optimiser launch runs the general kernel k_optimize<DynShape<D>> (as a whole-robot launch does;
+ * the shape-specialised k_lean kernels and the work queue have no moving variant) with a second obstacle
+ * table in LDS; where no trajectories-per-workgroup fits the 160 KiB the call is IRM_EINVAL (possible at
+ * N = 512 with many per-problem obstacles) — nothing falls back to the static table.
+ * Host-pointer entry points reject a non-finite velocity with IRM_EINVAL; the _dev entry points cannot see
+ * the values and do not check them.  irm_compute_cost_vg takes free points without times and stays static.
+ * Additive symbols: IRM_ABI_VERSION stays 3 and no struct changes layout; no reference counterpart. */
+int irm_eval_cost_moving(irm_ctx* ctx, const float* alpha, const float* start, const float* goal,
+                         const float* obstacles, int32_t n_obstacles, int32_t batch,
+                         float lambda_sg, float lambda_jl, float lambda_max, float* cost_out,
+                         const float* obstacle_velocity);
+int irm_eval_cost_grad_moving(irm_ctx* ctx, const float* alpha, const float* start, const float* goal,
+                              const float* obstacles, int32_t n_obstacles, int32_t batch,
+                              float lambda_sg, float lambda_jl, float lambda_max,
+                              float* grad_out, float* cost_out, const float* obstacle_velocity);
+int irm_optimize_batch_moving(irm_ctx* ctx, const float* alpha0, const float* start, const float* goal,
+                              const float* obstacles, int32_t n_obstacles, int32_t obstacle_stride,
+                              int32_t batch, float* alpha_out, float* traj_out, irm_stats* stats_out,
+                              float* series_out, const float* obstacle_velocity);
+/* Device pointers, enqueue-only on `stream`; the velocity table uses args->n_obstacles / obstacle_stride. */
+int irm_optimize_batch_moving_dev(irm_ctx* ctx, const irm_batch_dev* args, const float* obstacle_velocity_dev,
+                                  void* stream);
+int irm_dense_check_moving(irm_ctx* ctx, const float* alpha, const float* obstacles, int32_t n_obstacles,
+                           int32_t obstacle_stride, int32_t batch, irm_dense_report* report_out, float* cost_out,
+                           const float* obstacle_velocity);
+int irm_dense_check_moving_dev(irm_ctx* ctx, const float* alpha_dev, const float* obstacles_dev, int32_t n_obstacles,
+                               int32_t obstacle_stride, int32_t batch, irm_dense_report* report_dev, float* cost_dev,
+                               const float* obstacle_velocity_dev, void* stream);
+/* irm_optimize_plan for a moving launch of the same arguments: the kernel such a launch runs. */
+int irm_optimize_plan_moving(const irm_ctx* ctx, int32_t batch, int32_t n_obstacles, int32_t record_series,
+                             irm_launch_plan* out);
+
 /* Build id of the library: the first 16 hex digits of the SHA-256 over every file of
  * irm_motion_planning_amd/csrc and include/irm.h, the compile flags of every unit and the build
  * variant (build.py source_hash); "unknown" otherwise.

@@ -229,6 +229,38 @@ PROTOTYPES = {
     "irm_transfer_alpha_dev": (
         ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32, c_float_p, c_float_p, ctypes.c_void_p]
     ),
+    # moving obstacles: the static twins' arguments plus the velocity table (NULL: the static call)
+    "irm_eval_cost_moving": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_float, ctypes.c_float, ctypes.c_float, c_float_p, c_float_p],
+    ),
+    "irm_eval_cost_grad_moving": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_float, ctypes.c_float, ctypes.c_float, c_float_p, c_float_p, c_float_p],
+    ),
+    "irm_optimize_batch_moving": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, c_float_p, c_float_p, ctypes.POINTER(IrmStats), c_float_p, c_float_p],
+    ),
+    "irm_optimize_batch_moving_dev": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IrmBatchDev), c_float_p, ctypes.c_void_p]
+    ),
+    "irm_dense_check_moving": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+         ctypes.POINTER(IrmDenseReport), c_float_p, c_float_p],
+    ),
+    "irm_dense_check_moving_dev": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+         ctypes.POINTER(IrmDenseReport), c_float_p, c_float_p, ctypes.c_void_p],
+    ),
+    "irm_optimize_plan_moving": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(IrmLaunchPlan)]
+    ),
     "irm_build_id": (ctypes.c_char_p, []),
     "irm_debug_phase_profile": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
     "irm_debug_bls_trace_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),

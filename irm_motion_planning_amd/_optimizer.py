@@ -36,6 +36,11 @@ class _PersistentOptimizer:
             if hasattr(args, knob):
                 overrides.setdefault(knob, getattr(args, knob))
         self.env = Environment()
+        # --obstacle-velocity VX VY: every obstacle drifts by (VX, VY) over the plan (None: static obstacles)
+        self.obstacle_velocity = None
+        if getattr(args, "obstacle_velocity", None) is not None:
+            self.obstacle_velocity = np.broadcast_to(np.asarray(args.obstacle_velocity, np.float32),
+                                                     np.asarray(self.env.obstacles).shape).copy()
         self.trajectory = Trajectory(args, **overrides)
         self.context = self.trajectory.context
         self.last_stats = None
@@ -49,7 +54,7 @@ class _PersistentOptimizer:
     def optimize(self):
         t0 = time.perf_counter()
         res = self.context.optimize(self.env.start_config, self.env.goal_config, self.env.obstacles,
-                                    series=self.extendedVis)
+                                    series=self.extendedVis, obstacle_velocity=self.obstacle_velocity)
         self.last_profile = {"optimize_ms": 1000 * (time.perf_counter() - t0)}
         if self.extendedVis:
             alpha, traj, stats, series = res
@@ -67,14 +72,15 @@ class _PersistentOptimizer:
 
         Returns optimize_batch()'s result of the fine stage; self.last_stages keeps both stages:
         {"coarse": {"n_timesteps", "alpha", "stats"}, "fine": {"n_timesteps", "alpha0", "stats"}}."""
+        vel = self._velocity_for(obstacles)
         obstacles = self.env.obstacles if obstacles is None else obstacles
         D = self.trajectory.robot.N_joints
         start = np.asarray(start, np.float32).reshape(-1, D)
         goal = np.asarray(goal, np.float32).reshape(-1, D)
-        a_c, _, st_c = coarse.optimize(start, goal, obstacles)
+        a_c, _, st_c = coarse.optimize(start, goal, obstacles, obstacle_velocity=vel)
         self.context.set_transfer(coarse.N, rbf_variance_src=coarse.params.rbf_variance)
         alpha0 = self.context.transfer_alpha(a_c)
-        res = self.context.optimize(start, goal, obstacles, alpha0=alpha0, series=series)
+        res = self.context.optimize(start, goal, obstacles, alpha0=alpha0, series=series, obstacle_velocity=vel)
         self.last_stats = res[2]
         self.last_stages = {"coarse": {"n_timesteps": coarse.N, "alpha": a_c, "stats": st_c},
                             "fine": {"n_timesteps": self.context.N, "alpha0": alpha0, "stats": res[2]}}
@@ -85,10 +91,20 @@ class _PersistentOptimizer:
 
         Returns (alpha, traj, stats) — plus the B × S × N × D snapshot buffer with
         series=True (stats["series_len"] frames valid per problem)."""
+        vel = self._velocity_for(obstacles)
         obstacles = self.env.obstacles if obstacles is None else obstacles
         start = np.asarray(start, np.float32).reshape(-1, self.trajectory.robot.N_joints)
         goal = np.asarray(goal, np.float32).reshape(-1, self.trajectory.robot.N_joints)
         res = self.context.optimize(start, goal, obstacles, alpha0=alpha0, obstacle_stride=obstacle_stride,
-                                    series=series)
+                                    series=series, obstacle_velocity=vel)
         self.last_stats = res[2]
         return res
+
+    def _velocity_for(self, obstacles):
+        """The --obstacle-velocity table for `obstacles` (None: the environment's): the same drift for every
+        obstacle of every problem; None without the flag."""
+        if self.obstacle_velocity is None:
+            return None
+        if obstacles is None:
+            return self.obstacle_velocity
+        return np.broadcast_to(self.obstacle_velocity[0], np.asarray(obstacles).shape).copy()

@@ -111,11 +111,13 @@ class Context:
         d["build_id"] = d["build_id"].decode()
         return d
 
-    def launch_plan(self, batch, n_obstacles=0, series=False):
+    def launch_plan(self, batch, n_obstacles=0, series=False, obstacle_velocity=None):
         """The optimiser launch optimize() runs for `batch` problems (irm_optimize_plan: filled in by
-        the library's own launch dispatch, nothing launched)."""
+        the library's own launch dispatch, nothing launched).  obstacle_velocity not None: the launch of
+        a moving call (irm_optimize_plan_moving; only whether it is given matters)."""
         pl = IrmLaunchPlan()
-        check(self.lib.irm_optimize_plan(self._h, int(batch), int(n_obstacles), int(bool(series)), ctypes.byref(pl)))
+        fn = self.lib.irm_optimize_plan if obstacle_velocity is None else self.lib.irm_optimize_plan_moving
+        check(fn(self._h, int(batch), int(n_obstacles), int(bool(series)), ctypes.byref(pl)))
         d = {name: getattr(pl, name) for name, _ in IrmLaunchPlan._fields_}
         d["kernel"] = d["kernel"].decode()
         return d
@@ -191,10 +193,12 @@ class Context:
         check(self.lib.irm_eval_any(self._h, _ptr(a), a.shape[0], int(which), _ptr(out)))
         return out[0] if single else out
 
-    def dense_check(self, alpha, obstacles, with_cost=False):
+    def dense_check(self, alpha, obstacles, with_cost=False, obstacle_velocity=None):
         """Obstacle cost, joint and velocity limits on the evaluation times (irm_dense_check): a dict of
         arrays named as irm_dense_report's fields, plus `cost` ((B×)M per-sample cost) with with_cost.
-        obstacles: (O, 2) shared, or (B, O, 2) one table per problem, like optimize."""
+        obstacles: (O, 2) shared, or (B, O, 2) one table per problem, like optimize.
+        obstacle_velocity (the shape of obstacles): sample i sees obstacle o at p + t_eval[i]·w
+        (irm_dense_check_moving)."""
         a, single = self._batch(alpha, (self.N, self.D))
         B = a.shape[0]
         obs = _f32(obstacles)
@@ -209,7 +213,11 @@ class Context:
         M = int(self.lib.irm_eval_times(self._h, None))
         rep = (IrmDenseReport * B)()
         cost = np.zeros((B, max(M, 0)), np.float32) if with_cost else None
-        check(self.lib.irm_dense_check(self._h, _ptr(a), _ptr(obs), O, stride, B, rep, _ptr(cost)))
+        if obstacle_velocity is None:
+            check(self.lib.irm_dense_check(self._h, _ptr(a), _ptr(obs), O, stride, B, rep, _ptr(cost)))
+        else:
+            vel = self._velocity(obstacle_velocity, obs)
+            check(self.lib.irm_dense_check_moving(self._h, _ptr(a), _ptr(obs), O, stride, B, rep, _ptr(cost), _ptr(vel)))
         out = {}
         recs = np.frombuffer(rep, dtype=np.dtype(
             [(name, np.float32 if ctype is ctypes.c_float else np.int32) for name, ctype in IrmDenseReport._fields_]))
@@ -277,25 +285,45 @@ class Context:
         g = _f32(np.broadcast_to(_f32(goal), (B, self.D)))
         return s, g
 
-    def eval_cost(self, alpha, obstacles, start, goal, lsg, ljl, lmax):
+    @staticmethod
+    def _velocity(obstacle_velocity, obs):
+        """The velocity table of a moving call: fp32, the shape of the obstacle table `obs`."""
+        vel = _f32(obstacle_velocity)
+        if vel.shape != obs.shape:
+            raise ValueError(f"obstacle_velocity must have the obstacles' shape {obs.shape}, got {vel.shape}")
+        return vel
+
+    def eval_cost(self, alpha, obstacles, start, goal, lsg, ljl, lmax, obstacle_velocity=None):
+        """obstacle_velocity (O×2): waypoint n sees obstacle o at p + t[n]·w (irm_eval_cost_moving)."""
         a, single = self._batch(alpha, (self.N, self.D))
         B = a.shape[0]
         s, g = self._sg(start, goal, B)
         obs = _f32(obstacles).reshape(-1, 2)
         out = np.zeros(B, np.float32)
-        check(self.lib.irm_eval_cost(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
-                                     float(lsg), float(ljl), float(lmax), _ptr(out)))
+        if obstacle_velocity is None:
+            check(self.lib.irm_eval_cost(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
+                                         float(lsg), float(ljl), float(lmax), _ptr(out)))
+        else:
+            vel = self._velocity(_f32(obstacle_velocity).reshape(-1, 2), obs)
+            check(self.lib.irm_eval_cost_moving(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
+                                                float(lsg), float(ljl), float(lmax), _ptr(out), _ptr(vel)))
         return out[0] if single else out
 
-    def eval_cost_grad(self, alpha, obstacles, start, goal, lsg, ljl, lmax, with_cost=False):
+    def eval_cost_grad(self, alpha, obstacles, start, goal, lsg, ljl, lmax, with_cost=False, obstacle_velocity=None):
         a, single = self._batch(alpha, (self.N, self.D))
         B = a.shape[0]
         s, g = self._sg(start, goal, B)
         obs = _f32(obstacles).reshape(-1, 2)
         grad = np.zeros_like(a)
         cost = np.zeros(B, np.float32)
-        check(self.lib.irm_eval_cost_grad(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
-                                          float(lsg), float(ljl), float(lmax), _ptr(grad), _ptr(cost)))
+        if obstacle_velocity is None:
+            check(self.lib.irm_eval_cost_grad(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
+                                              float(lsg), float(ljl), float(lmax), _ptr(grad), _ptr(cost)))
+        else:
+            vel = self._velocity(_f32(obstacle_velocity).reshape(-1, 2), obs)
+            check(self.lib.irm_eval_cost_grad_moving(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
+                                                     float(lsg), float(ljl), float(lmax), _ptr(grad), _ptr(cost),
+                                                     _ptr(vel)))
         if single:
             grad, cost = grad[0], cost[0]
         return (grad, cost) if with_cost else grad
@@ -343,8 +371,10 @@ class Context:
             cg = None if cg is None else cg[0]
         return (cv, cg) if with_grad else cv
 
-    def optimize(self, start, goal, obstacles, alpha0=None, obstacle_stride=0, series=False):
-        """Batched Optimizer.optimize(): returns (alpha, traj, stats[, series])."""
+    def optimize(self, start, goal, obstacles, alpha0=None, obstacle_stride=0, series=False, obstacle_velocity=None):
+        """Batched Optimizer.optimize(): returns (alpha, traj, stats[, series]).
+        obstacle_velocity (the shape of obstacles): the optimiser minimises the cost in which waypoint n
+        sees obstacle o at p + t[n]·w (irm_optimize_batch_moving)."""
         s, single = self._batch(start, (self.D,))
         g, _ = self._batch(goal, (self.D,))
         B = s.shape[0]
@@ -368,8 +398,14 @@ class Context:
         stats = (IrmStats * B)()
         cap = self.series_capacity() if series else 0
         ser = np.zeros((B, cap, self.N, self.D), np.float32) if series else None
-        check(self.lib.irm_optimize_batch(self._h, _ptr(a0), _ptr(s), _ptr(g), _ptr(obs), O, int(obstacle_stride),
-                                          B, _ptr(alpha), _ptr(traj), stats, _ptr(ser)))
+        if obstacle_velocity is None:
+            check(self.lib.irm_optimize_batch(self._h, _ptr(a0), _ptr(s), _ptr(g), _ptr(obs), O, int(obstacle_stride),
+                                              B, _ptr(alpha), _ptr(traj), stats, _ptr(ser)))
+        else:
+            vel = self._velocity(obstacle_velocity, obs)
+            check(self.lib.irm_optimize_batch_moving(self._h, _ptr(a0), _ptr(s), _ptr(g), _ptr(obs), O,
+                                                     int(obstacle_stride), B, _ptr(alpha), _ptr(traj), stats, _ptr(ser),
+                                                     _ptr(vel)))
         st = stats_to_dict(stats)
         if single:
             alpha, traj = alpha[0], traj[0]
@@ -395,15 +431,25 @@ class Context:
             check(n)
         return out[: min(int(n_trials), n)]
 
-    def optimize_dev(self, batch_dev, stream=0):
-        """Enqueue irm_optimize_batch_dev with device pointers (IrmBatchDev)."""
-        check(self.lib.irm_optimize_batch_dev(self._h, ctypes.byref(batch_dev), ctypes.c_void_p(stream)))
+    def optimize_dev(self, batch_dev, stream=0, obstacle_velocity_dev=0):
+        """Enqueue irm_optimize_batch_dev with device pointers (IrmBatchDev).  obstacle_velocity_dev: the
+        device address of the velocity table (the batch's n_obstacles / obstacle_stride), or the
+        `obstacle_velocity` that batch_dev() was given; 0: the static launch."""
+        vel = obstacle_velocity_dev or getattr(batch_dev, "obstacle_velocity", 0)
+        if not vel:
+            check(self.lib.irm_optimize_batch_dev(self._h, ctypes.byref(batch_dev), ctypes.c_void_p(stream)))
+        else:
+            check(self.lib.irm_optimize_batch_moving_dev(self._h, ctypes.byref(batch_dev), _dev(vel),
+                                                         ctypes.c_void_p(stream)))
 
 
 def batch_dev(alpha0=0, start=0, goal=0, obstacles=0, n_obstacles=0, obstacle_stride=0, batch=0, alpha_out=0,
-              traj_out=0, stats_out=0, series_out=0):
-    """Build an IrmBatchDev from raw device addresses (e.g. torch data_ptr())."""
+              traj_out=0, stats_out=0, series_out=0, obstacle_velocity=0):
+    """Build an IrmBatchDev from raw device addresses (e.g. torch data_ptr()).  obstacle_velocity: the device
+    address of the velocity table of a moving launch; it is no field of irm_batch_dev (the struct keeps its
+    layout) and rides along as an attribute that Context.optimize_dev passes to the moving entry point."""
     b = IrmBatchDev()
+    b.obstacle_velocity = int(obstacle_velocity or 0)
     b.alpha0, b.start, b.goal, b.obstacles = alpha0 or None, start, goal, obstacles
     b.n_obstacles, b.obstacle_stride, b.batch = n_obstacles, obstacle_stride, batch
     b.alpha_out, b.traj_out, b.stats_out, b.series_out = alpha_out or None, traj_out or None, stats_out or None, \

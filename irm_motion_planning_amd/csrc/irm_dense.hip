@@ -128,6 +128,8 @@ constexpr int kDenseRedW = 8;  // words per wave of the cross-wave combine
 // context's cost variant), the per-sample cost (optional) and the report.  Each wave reduces its 64
 // samples of a chunk with the DPP trees and folds them into its running values in chunk order; the
 // waves' values are combined from LDS in wave order.  Ties go to the lower index (amax_step).
+// A moving launch (P.moving, irm_dense_check_moving): sample i sees the obstacle table at its own time
+// t_eval[i] (P.tsup: the evaluation times on the device), from the velocity table staged behind the positions.
 template <int D>
 __global__ __launch_bounds__(kDenseT) void k_dense_check(KParams P, const float* kqT, const float* dkqT, int M,
                                                          irm_dense_report* rep, float* cost) {
@@ -137,9 +139,10 @@ __global__ __launch_bounds__(kDenseT) void k_dense_check(KParams P, const float*
     const int b = blockIdx.x;
     float* Al = smem;
     float* obsL = smem + al4(P.N * D);
-    float* red = obsL + obs_pitch(P.O) + 4;
+    float* red = obsL + (P.moving ? 2 : 1) * obs_pitch(P.O) + 4;
+    const float* velL = obsL + obs_pitch(P.O);
     dense_stage_alpha<D>(P, b, Al);
-    stage_obstacles(P, b, 1, obsL);  // (the launch sets TB = 1, BT = kDenseT)
+    stage_obstacles<true>(P, b, 1, obsL);  // (the launch sets TB = 1, BT = kDenseT)
     __syncthreads();
     float cmax = -INFINITY, csum = 0.f, tx = -INFINITY, tn = INFINITY, va = -INFINITY;
     int cidx = 0x7fffffff, vidx = 0x7fffffff;
@@ -149,7 +152,7 @@ __global__ __launch_bounds__(kDenseT) void k_dense_check(KParams P, const float*
         float q[D], v[D];
         dense_sample<D, true>(P, Al, kqT, dkqT, (unsigned)M, (unsigned)(live ? i : M - 1), q, v);
         WP<D> w;
-        eval_waypoint_rt<D>(P, q, v, obsL, w);
+        eval_waypoint_rt<D>(P, q, v, obsL, w, velL, P.moving ? P.tsup[live ? i : M - 1] : 0.f);
         if (cost && live) cost[(size_t)b * M + i] = w.cv;
         float c = live ? w.cv : -INFINITY, a = live ? w.va : -INFINITY;
         int ci = live ? i : 0x7fffffff, ai = ci;
@@ -200,7 +203,7 @@ __global__ __launch_bounds__(kDenseT) void k_dense_check(KParams P, const float*
 
 static size_t dense_lds(const KParams& p, bool check) {
     int words = al4(p.N * p.D);
-    if (check) words += obs_pitch(p.O) + 4 + (kDenseT / 64) * kDenseRedW;
+    if (check) words += (p.moving ? 2 : 1) * obs_pitch(p.O) + 4 + (kDenseT / 64) * kDenseRedW;
     return (size_t)words * 4;
 }
 

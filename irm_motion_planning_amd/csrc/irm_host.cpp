@@ -80,6 +80,9 @@ struct irm_ctx {
     // the device, transposed ([N][M])
     std::vector<float> t_eval;
     float *d_KqT = nullptr, *d_dKqT = nullptr;
+    // moving obstacles: the support times t[n] on the device (kp.tsup, uploaded once at creation) and the
+    // evaluation times of irm_dense_check_moving (with the query matrices)
+    float *d_t = nullptr, *d_teval = nullptr;
     // fitting and re-timing (irm_fit_alpha, irm_transfer_alpha): the ridge ρ, the Cholesky factor of K + ρI
     // (extended precision, see fit_factor; empty until first use), Wᵀ and Tᵀ on the device in fp64 ([source row][waypoint]) and the source grid's
     // fp32 query row at t0 (xfer_src = 0: no transfer set)
@@ -238,6 +241,11 @@ int irm_ctx_create(irm_ctx** out, const irm_params* p) {
     }
     if (const char* err = irm::fill_kparams(*p, ops, kp)) return fail(IRM_EINVAL, "%s", err);
     c->t = std::move(ops.t);  // kept for irm_kernel_matrices, the eval times and the fit
+    if (upload(&c->d_t, c->t)) {
+        std::string e = g_err;
+        return fail(IRM_ENOMEM, "%s", e.c_str());
+    }
+    kp.tsup = c->d_t;
     c->K = std::move(ops.K);
     c->dK = std::move(ops.dK);
     c->J = std::move(ops.J);
@@ -270,6 +278,8 @@ void irm_ctx_destroy(irm_ctx* c) {
     if (c->d_queue) (void)hipFree(c->d_queue);
     if (c->d_KqT) (void)hipFree(c->d_KqT);
     if (c->d_dKqT) (void)hipFree(c->d_dKqT);
+    if (c->d_t) (void)hipFree(c->d_t);
+    if (c->d_teval) (void)hipFree(c->d_teval);
     if (c->d_WT) (void)hipFree(c->d_WT);
     if (c->d_TT) (void)hipFree(c->d_TT);
     if (c->d_kq0) (void)hipFree(c->d_kq0);
@@ -370,19 +380,35 @@ int check_stride(int O, int stride) {
     return 0;
 }
 
-// Run one forward-family kernel on B host trajectories.
+// a host velocity table (n floats): every entry finite
+int check_vel(const char* fn, const float* vel, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(vel[i])) return fail(IRM_EINVAL, "%s: obstacle_velocity[%zu] is not finite", fn, i);
+    return 0;
+}
+
+// a moving launch for which choose_shape found no trajectories-per-workgroup
+int fail_moving_lds(const char* fn, const irm_ctx* c, int O, int stride) {
+    return fail(IRM_EINVAL, "%s: no workgroup shape fits the 160 KiB LDS for N=%d with O=%d %s obstacles and the moving "
+                "table (positions and velocities: twice the obstacle words)", fn, c->N, O, stride ? "per-problem" : "shared");
+}
+
+// Run one forward-family kernel on B host trajectories.  vel (nullable): the obstacles' velocities (O×2).
 int run_forward(irm_ctx* c, int mode, const float* alpha, const float* start, const float* goal, const float* obs,
-                int O, int B, float lsg, float ljl, float lmax, int which, float* out0, float* out1, uint8_t* ok) {
+                int O, int B, float lsg, float ljl, float lmax, int which, float* out0, float* out1, uint8_t* ok,
+                const float* vel = nullptr) {
     if (set_device(c)) return IRM_EDEVICE;
     if (B < 0 || !alpha) return fail(IRM_EINVAL, "bad batch arguments");
     if (check_obs(O)) return IRM_EINVAL;
+    if (!obs || O == 0) vel = nullptr;  // no obstacle, nothing moves
+    if (vel && check_vel("irm_eval_cost(_grad)_moving", vel, (size_t)O * 2)) return IRM_EINVAL;
     if (B == 0) return IRM_OK;
     const int N = c->N, D = c->D;
     const size_t nd = (size_t)B * N * D;
     Stage st{c};
     const size_t o_alpha = st.take(nd * 4), o_s = st.take((size_t)B * D * 4), o_g = st.take((size_t)B * D * 4),
                  o_obs = st.take((size_t)std::max(O, 1) * 8), o_out0 = st.take(std::max(nd, (size_t)B * 11) * 4),
-                 o_out1 = st.take(nd * 4), o_ok = st.take((size_t)B);
+                 o_out1 = st.take(nd * 4), o_ok = st.take((size_t)B), o_vel = st.take((size_t)std::max(O, 1) * 8);
     if (ensure_io(c, st.off)) return IRM_ENOMEM;
     char* d = st.base();
     hipStream_t s = c->stream;
@@ -392,10 +418,15 @@ int run_forward(irm_ctx* c, int mode, const float* alpha, const float* start, co
     HIP_TRY(hipMemcpyAsync(d + o_s, start ? start : zeros.data(), (size_t)B * D * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_g, goal ? goal : zeros.data(), (size_t)B * D * 4, hipMemcpyHostToDevice, s));
     if (O > 0 && obs) HIP_TRY(hipMemcpyAsync(d + o_obs, obs, (size_t)O * 8, hipMemcpyHostToDevice, s));
+    if (vel) HIP_TRY(hipMemcpyAsync(d + o_vel, vel, (size_t)O * 8, hipMemcpyHostToDevice, s));
     KParams kp = c->kp;
     kp.B = B;
     kp.O = (obs ? O : 0);
     kp.obs_stride = 0;
+    if (vel) {
+        kp.moving = 1;
+        kp.obs_vel = (const float*)(d + o_vel);
+    }
     kp.alpha0 = (const float*)(d + o_alpha);
     kp.start = (const float*)(d + o_s);
     kp.goal = (const float*)(d + o_g);
@@ -408,7 +439,8 @@ int run_forward(irm_ctx* c, int mode, const float* alpha, const float* start, co
     kp.out0 = (float*)(d + o_out0);
     kp.out1 = (float*)(d + o_out1);
     kp.out_ok = (uint8_t*)(d + o_ok);
-    if (choose_shape(c, B, false, kp, nullptr) <= 0) return fail(IRM_EINVAL, "no workgroup shape fits LDS");
+    if (choose_shape(c, B, false, kp, nullptr) <= 0)
+        return vel ? fail_moving_lds("irm_eval_cost(_grad)_moving", c, O, 0) : fail(IRM_EINVAL, "no workgroup shape fits LDS");
     HIP_TRY(irm::launch_forward(kp, mode, s));
     if (out0) {
         size_t bytes = (mode == 0) ? nd * 4 : (mode == 3 ? (size_t)B * 11 * 4 : (size_t)B * 4);
@@ -438,6 +470,22 @@ int irm_eval_cost_grad(irm_ctx* c, const float* alpha, const float* start, const
                        int32_t O, int32_t B, float lsg, float ljl, float lmax, float* grad_out, float* cost_out) {
     if (!c || !grad_out || !start || !goal) return fail(IRM_EINVAL, "irm_eval_cost_grad: null argument");
     return run_forward(c, 2, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, grad_out, nullptr);
+}
+
+int irm_eval_cost_moving(irm_ctx* c, const float* alpha, const float* start, const float* goal, const float* obstacles,
+                         int32_t O, int32_t B, float lsg, float ljl, float lmax, float* cost_out,
+                         const float* obstacle_velocity) {
+    if (!c || !cost_out || !start || !goal) return fail(IRM_EINVAL, "irm_eval_cost_moving: null argument");
+    return run_forward(c, 1, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, nullptr, nullptr,
+                       obstacle_velocity);
+}
+
+int irm_eval_cost_grad_moving(irm_ctx* c, const float* alpha, const float* start, const float* goal,
+                              const float* obstacles, int32_t O, int32_t B, float lsg, float ljl, float lmax,
+                              float* grad_out, float* cost_out, const float* obstacle_velocity) {
+    if (!c || !grad_out || !start || !goal) return fail(IRM_EINVAL, "irm_eval_cost_grad_moving: null argument");
+    return run_forward(c, 2, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, grad_out, nullptr,
+                       obstacle_velocity);
 }
 
 int irm_constraints(irm_ctx* c, const float* alpha, const float* start, const float* goal, int32_t B, uint8_t* ok_out,
@@ -534,7 +582,12 @@ int irm_init_alpha(irm_ctx* c, const float* start, const float* goal, int32_t B,
     return IRM_OK;
 }
 
-int irm_optimize_batch_dev(irm_ctx* c, const irm_batch_dev* a, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// irm_optimize_batch_dev / irm_optimize_batch_moving_dev (vel: device pointer, NULL for the static launch)
+int optimize_dev(irm_ctx* c, const irm_batch_dev* a, const float* vel, void* stream) {
     if (!c || !a) return fail(IRM_EINVAL, "irm_optimize_batch_dev: null argument");
     if (a->batch < 0 || !a->start || !a->goal) return fail(IRM_EINVAL, "bad batch arguments");
     if (check_obs(a->n_obstacles) || check_stride(a->n_obstacles, a->obstacle_stride)) return IRM_EINVAL;
@@ -555,7 +608,13 @@ int irm_optimize_batch_dev(irm_ctx* c, const irm_batch_dev* a, void* stream) {
     kp.series = a->series_out;
     kp.trace = c->d_trace;
     kp.trace_cap = c->trace_cap;
-    if (choose_shape(c, a->batch, true, kp, nullptr) <= 0) return fail(IRM_EINVAL, "no workgroup shape fits LDS");
+    if (vel && a->n_obstacles > 0) {
+        kp.moving = 1;
+        kp.obs_vel = vel;
+    }
+    if (choose_shape(c, a->batch, true, kp, nullptr) <= 0)
+        return kp.moving ? fail_moving_lds("irm_optimize_batch_moving", c, a->n_obstacles, a->obstacle_stride)
+                         : fail(IRM_EINVAL, "no workgroup shape fits LDS");
 #if defined(IRM_PHASE_PROFILE) || defined(IRM_DIV_CHECK)
     {  // (IRM_DIV_CHECK: per-block counters of the BLS division check, zeroed per launch)
         const int grid = (a->batch + kp.TB - 1) / kp.TB;
@@ -576,8 +635,8 @@ int irm_optimize_batch_dev(irm_ctx* c, const irm_batch_dev* a, void* stream) {
     return IRM_OK;
 }
 
-int irm_optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series,
-                      irm_launch_plan* out) {
+int optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series, bool moving,
+                  irm_launch_plan* out) {
     if (!c || !out || batch <= 0) return fail(IRM_EINVAL, "irm_optimize_plan: bad argument");
     if (check_obs(n_obstacles)) return IRM_EINVAL;
     memset(out, 0, sizeof(*out));
@@ -587,7 +646,10 @@ int irm_optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int3
     // the series flow runs when the context records it (irm_params.record_series) or the call asks
     // for the series (irm_optimize_batch with series_out) — as in irm_optimize_batch(_dev)
     kp.record_series = (c->kp.record_series || record_series) ? 1 : 0;
-    if (choose_shape(c, batch, true, kp, nullptr) <= 0) return fail(IRM_EINVAL, "no workgroup shape fits LDS");
+    kp.moving = (moving && n_obstacles > 0) ? 1 : 0;
+    if (choose_shape(c, batch, true, kp, nullptr) <= 0)
+        return kp.moving ? fail_moving_lds("irm_optimize_plan_moving", c, n_obstacles, 0)
+                         : fail(IRM_EINVAL, "no workgroup shape fits LDS");
     irm::LaunchDesc d{};
     d.describe_only = true;
     HIP_TRY(irm::launch_optimize(kp, nullptr, &d));  // the dispatch fills d and launches nothing
@@ -605,6 +667,26 @@ int irm_optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int3
     out->lam16 = c->lam16;
     out->lam24 = c->lam24;
     return IRM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int irm_optimize_batch_dev(irm_ctx* c, const irm_batch_dev* a, void* stream) { return optimize_dev(c, a, nullptr, stream); }
+
+int irm_optimize_batch_moving_dev(irm_ctx* c, const irm_batch_dev* a, const float* obstacle_velocity_dev, void* stream) {
+    return optimize_dev(c, a, obstacle_velocity_dev, stream);
+}
+
+int irm_optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series,
+                      irm_launch_plan* out) {
+    return optimize_plan(c, batch, n_obstacles, record_series, false, out);
+}
+
+int irm_optimize_plan_moving(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series,
+                             irm_launch_plan* out) {
+    return optimize_plan(c, batch, n_obstacles, record_series, true, out);
 }
 
 int irm_set_work_queue(irm_ctx* c, int32_t groups) {
@@ -676,7 +758,11 @@ int irm_set_eval_times(irm_ctx* c, const float* t_eval, int32_t M) {
     if (c->d_dKqT) (void)hipFree(c->d_dKqT);
     c->d_KqT = c->d_dKqT = nullptr;
     c->t_eval.clear();
-    if (upload(&c->d_KqT, kqT) || upload(&c->d_dKqT, dkqT)) return IRM_ENOMEM;
+    if (c->d_teval) (void)hipFree(c->d_teval);
+    c->d_teval = nullptr;
+    if (upload(&c->d_KqT, kqT) || upload(&c->d_dKqT, dkqT) ||
+        upload(&c->d_teval, std::vector<float>(t_eval, t_eval + M)))
+        return IRM_ENOMEM;
     c->t_eval.assign(t_eval, t_eval + M);
     return IRM_OK;
 }
@@ -710,8 +796,13 @@ int irm_eval_any(irm_ctx* c, const float* alpha, int32_t B, int32_t which, float
     return IRM_OK;
 }
 
-int irm_dense_check_dev(irm_ctx* c, const float* alpha, const float* obstacles, int32_t O, int32_t obstacle_stride,
-                        int32_t B, irm_dense_report* report, float* cost, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// irm_dense_check(_moving)_dev: vel a device pointer, NULL for the static check
+int dense_check_dev(irm_ctx* c, const float* alpha, const float* obstacles, int32_t O, int32_t obstacle_stride,
+                    int32_t B, irm_dense_report* report, float* cost, const float* vel, void* stream) {
     if (!c || !alpha || !report) return fail(IRM_EINVAL, "irm_dense_check_dev: null argument");
     if (c->t_eval.empty()) return fail(IRM_EINVAL, "irm_dense_check_dev: no evaluation times set (irm_set_eval_times)");
     if (B < 0) return fail(IRM_EINVAL, "irm_dense_check_dev: negative batch");
@@ -725,12 +816,17 @@ int irm_dense_check_dev(irm_ctx* c, const float* alpha, const float* obstacles, 
     kp.obs_stride = obstacle_stride;
     kp.alpha0 = alpha;
     kp.obstacles = obstacles;
+    if (vel && O > 0) {  // sample i sees the table at t_eval[i]
+        kp.moving = 1;
+        kp.obs_vel = vel;
+        kp.tsup = c->d_teval;
+    }
     HIP_TRY(irm::launch_dense_check(kp, c->d_KqT, c->d_dKqT, (int)c->t_eval.size(), report, cost, (hipStream_t)stream));
     return IRM_OK;
 }
 
-int irm_dense_check(irm_ctx* c, const float* alpha, const float* obstacles, int32_t O, int32_t obstacle_stride,
-                    int32_t B, irm_dense_report* report_out, float* cost_out) {
+int dense_check_host(irm_ctx* c, const float* alpha, const float* obstacles, int32_t O, int32_t obstacle_stride,
+                     int32_t B, irm_dense_report* report_out, float* cost_out, const float* vel) {
     if (!c || !alpha || !report_out) return fail(IRM_EINVAL, "irm_dense_check: null argument");
     if (c->t_eval.empty()) return fail(IRM_EINVAL, "irm_dense_check: no evaluation times set (irm_set_eval_times)");
     if (B < 0) return fail(IRM_EINVAL, "irm_dense_check: negative batch");
@@ -742,20 +838,50 @@ int irm_dense_check(irm_ctx* c, const float* alpha, const float* obstacles, int3
     const size_t nd = (size_t)B * N * D;
     const size_t nobs = obstacle_stride ? (size_t)B * obstacle_stride : (size_t)O * 2;
     Stage st{c};
+    if (O == 0) vel = nullptr;
+    if (vel && check_vel("irm_dense_check_moving", vel, nobs)) return IRM_EINVAL;
     const size_t o_a = st.take(nd * 4), o_o = st.take(std::max<size_t>(nobs, 1) * 4),
-                 o_r = st.take((size_t)B * sizeof(irm_dense_report)), o_c = st.take((size_t)B * M * 4);
+                 o_r = st.take((size_t)B * sizeof(irm_dense_report)), o_c = st.take((size_t)B * M * 4),
+                 o_w = st.take(std::max<size_t>(nobs, 1) * 4);
     if (ensure_io(c, st.off)) return IRM_ENOMEM;
     char* d = st.base();
     hipStream_t s = c->stream;
     HIP_TRY(hipMemcpyAsync(d + o_a, alpha, nd * 4, hipMemcpyHostToDevice, s));
     if (nobs && O > 0) HIP_TRY(hipMemcpyAsync(d + o_o, obstacles, nobs * 4, hipMemcpyHostToDevice, s));
-    const int rc = irm_dense_check_dev(c, (const float*)(d + o_a), (const float*)(d + o_o), O, obstacle_stride, B,
-                                       (irm_dense_report*)(d + o_r), cost_out ? (float*)(d + o_c) : nullptr, s);
+    if (vel) HIP_TRY(hipMemcpyAsync(d + o_w, vel, nobs * 4, hipMemcpyHostToDevice, s));
+    const int rc = dense_check_dev(c, (const float*)(d + o_a), (const float*)(d + o_o), O, obstacle_stride, B,
+                                   (irm_dense_report*)(d + o_r), cost_out ? (float*)(d + o_c) : nullptr,
+                                   vel ? (const float*)(d + o_w) : nullptr, s);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(report_out, d + o_r, (size_t)B * sizeof(irm_dense_report), hipMemcpyDeviceToHost, s));
     if (cost_out) HIP_TRY(hipMemcpyAsync(cost_out, d + o_c, (size_t)B * M * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return IRM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int irm_dense_check_dev(irm_ctx* c, const float* alpha, const float* obstacles, int32_t O, int32_t obstacle_stride,
+                        int32_t B, irm_dense_report* report, float* cost, void* stream) {
+    return dense_check_dev(c, alpha, obstacles, O, obstacle_stride, B, report, cost, nullptr, stream);
+}
+
+int irm_dense_check(irm_ctx* c, const float* alpha, const float* obstacles, int32_t O, int32_t obstacle_stride,
+                    int32_t B, irm_dense_report* report_out, float* cost_out) {
+    return dense_check_host(c, alpha, obstacles, O, obstacle_stride, B, report_out, cost_out, nullptr);
+}
+
+int irm_dense_check_moving_dev(irm_ctx* c, const float* alpha, const float* obstacles, int32_t O,
+                               int32_t obstacle_stride, int32_t B, irm_dense_report* report, float* cost,
+                               const float* obstacle_velocity_dev, void* stream) {
+    return dense_check_dev(c, alpha, obstacles, O, obstacle_stride, B, report, cost, obstacle_velocity_dev, stream);
+}
+
+int irm_dense_check_moving(irm_ctx* c, const float* alpha, const float* obstacles, int32_t O, int32_t obstacle_stride,
+                           int32_t B, irm_dense_report* report_out, float* cost_out, const float* obstacle_velocity) {
+    return dense_check_host(c, alpha, obstacles, O, obstacle_stride, B, report_out, cost_out, obstacle_velocity);
 }
 
 // ------------------------------------------------- fitting and re-timing
@@ -1060,9 +1186,13 @@ const char* irm_build_id(void) {
 #endif
 }
 
-int irm_optimize_batch(irm_ctx* c, const float* alpha0, const float* start, const float* goal, const float* obstacles,
-                       int32_t O, int32_t obstacle_stride, int32_t B, float* alpha_out, float* traj_out,
-                       irm_stats* stats_out, float* series_out) {
+}  // extern "C"
+
+namespace {
+
+int optimize_host(irm_ctx* c, const float* alpha0, const float* start, const float* goal, const float* obstacles,
+                  int32_t O, int32_t obstacle_stride, int32_t B, float* alpha_out, float* traj_out,
+                  irm_stats* stats_out, float* series_out, const float* vel) {
     if (!c || !start || !goal) return fail(IRM_EINVAL, "irm_optimize_batch: null argument");
     if (check_obs(O) || check_stride(O, obstacle_stride)) return IRM_EINVAL;
     if (set_device(c)) return IRM_EDEVICE;
@@ -1071,10 +1201,13 @@ int irm_optimize_batch(irm_ctx* c, const float* alpha0, const float* start, cons
     const size_t nd = (size_t)B * N * D;
     const size_t nobs = obstacle_stride ? (size_t)B * obstacle_stride : (size_t)O * 2;
     const size_t nser = series_out ? (size_t)B * c->max_series * N * D : 0;
+    if (!obstacles || O == 0) vel = nullptr;
+    if (vel && check_vel("irm_optimize_batch_moving", vel, nobs)) return IRM_EINVAL;
     Stage st{c};
     const size_t o_a0 = st.take(nd * 4), o_s = st.take((size_t)B * D * 4), o_g = st.take((size_t)B * D * 4),
                  o_o = st.take(std::max<size_t>(nobs, 1) * 4), o_ao = st.take(nd * 4), o_to = st.take(nd * 4),
-                 o_st = st.take((size_t)B * sizeof(irm_stats)), o_se = st.take(std::max<size_t>(nser, 1) * 4);
+                 o_st = st.take((size_t)B * sizeof(irm_stats)), o_se = st.take(std::max<size_t>(nser, 1) * 4),
+                 o_w = st.take(std::max<size_t>(nobs, 1) * 4);
     if (ensure_io(c, st.off)) return IRM_ENOMEM;
     char* d = st.base();
     hipStream_t s = c->stream;
@@ -1082,6 +1215,7 @@ int irm_optimize_batch(irm_ctx* c, const float* alpha0, const float* start, cons
     HIP_TRY(hipMemcpyAsync(d + o_s, start, (size_t)B * D * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_g, goal, (size_t)B * D * 4, hipMemcpyHostToDevice, s));
     if (nobs && obstacles) HIP_TRY(hipMemcpyAsync(d + o_o, obstacles, nobs * 4, hipMemcpyHostToDevice, s));
+    if (vel) HIP_TRY(hipMemcpyAsync(d + o_w, vel, nobs * 4, hipMemcpyHostToDevice, s));
     irm_batch_dev a{};
     a.alpha0 = alpha0 ? (const float*)(d + o_a0) : nullptr;
     a.start = (const float*)(d + o_s);
@@ -1096,7 +1230,7 @@ int irm_optimize_batch(irm_ctx* c, const float* alpha0, const float* start, cons
     a.series_out = series_out ? (float*)(d + o_se) : nullptr;
     KParams save = c->kp;
     if (series_out) c->kp.record_series = 1;
-    int rc = irm_optimize_batch_dev(c, &a, s);
+    int rc = optimize_dev(c, &a, vel ? (const float*)(d + o_w) : nullptr, s);
     c->kp = save;
     if (rc) return rc;
     if (alpha_out) HIP_TRY(hipMemcpyAsync(alpha_out, d + o_ao, nd * 4, hipMemcpyDeviceToHost, s));
@@ -1105,6 +1239,25 @@ int irm_optimize_batch(irm_ctx* c, const float* alpha0, const float* start, cons
     if (series_out) HIP_TRY(hipMemcpyAsync(series_out, d + o_se, nser * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return IRM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int irm_optimize_batch(irm_ctx* c, const float* alpha0, const float* start, const float* goal, const float* obstacles,
+                       int32_t O, int32_t obstacle_stride, int32_t B, float* alpha_out, float* traj_out,
+                       irm_stats* stats_out, float* series_out) {
+    return optimize_host(c, alpha0, start, goal, obstacles, O, obstacle_stride, B, alpha_out, traj_out, stats_out,
+                         series_out, nullptr);
+}
+
+int irm_optimize_batch_moving(irm_ctx* c, const float* alpha0, const float* start, const float* goal,
+                              const float* obstacles, int32_t O, int32_t obstacle_stride, int32_t B, float* alpha_out,
+                              float* traj_out, irm_stats* stats_out, float* series_out,
+                              const float* obstacle_velocity) {
+    return optimize_host(c, alpha0, start, goal, obstacles, O, obstacle_stride, B, alpha_out, traj_out, stats_out,
+                         series_out, obstacle_velocity);
 }
 
 }  // extern "C"

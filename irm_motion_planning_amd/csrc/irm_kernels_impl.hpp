@@ -259,11 +259,17 @@ __device__ __forceinline__ void lean_pen(const KParams& P, const float (&q)[D], 
 // zm = mask·(q − μ)/σ_q and zvm = mask·v/v_max per joint, w.jp = Σ zm², w.jv = Σ zvm² (the ½ and the
 // 1/N of trajectory.py:215-227, 245-255 go into the per-trajectory weights, grad_waypoint_lean); the
 // host-API kernels keep the reference's element order (½·z² per element, summed).
-template <int D, bool WHOLE = false, bool POT = true, bool LEAN = false>
+// MOVING: every obstacle drifts at a constant velocity over the plan; the lane's waypoint lies at plan time
+// tau and sees obstacle o at fmaf(tau, w_o, p_o) per coordinate — one packed FMA per coordinate pair of an
+// obstacle pair, from the velocity table `vel` (LDS, stage_obstacles' layout; sentinel velocity 0, so the
+// padding stays at 1e20 and adds exactly 0).  From there on the arithmetic is the static one's; a zero
+// velocity gives the static result to the bit (fmaf(tau, 0, p) = p).
+template <int D, bool WHOLE = false, bool POT = true, bool LEAN = false, bool MOVING = false>
 __device__ __forceinline__ void eval_waypoint(const KParams& P, const float (&q)[D], const float (&v)[D],
                                               const float* __restrict__ ob, WP<D>& w,
-                                              const f32x4* oreg = nullptr) {  // oreg: the 12-obstacle
-                                                                              // table held in VGPRs
+                                              const f32x4* oreg = nullptr,  // oreg: the 12-obstacle
+                                                                            // table held in VGPRs
+                                              const float* __restrict__ vel = nullptr, float tau = 0.f) {
     float fx = 0.f, fy = 0.f, Sx = 0.f, Sy = 0.f;
     float xs[D], ys[D], px[D], py[D], cum[D], snv[D], csv[D];
     bool big = false;
@@ -303,6 +309,17 @@ __device__ __forceinline__ void eval_waypoint(const KParams& P, const float (&q)
     // obstacles accumulate separately and are added at the end.
     const f32x4* o4 = reinterpret_cast<const f32x4*>(ob);
     const int nq = (P.O + 3) >> 2;
+    // obstacle pair i (x_a, x_b, y_a, y_b) at this lane's time
+    auto pair_at = [&](int i) -> f32x4 {
+        f32x4 p = o4[i];
+        if constexpr (MOVING) {
+            const f32x4 wv = reinterpret_cast<const f32x4*>(vel)[i];
+            const f32x2 t2 = {tau, tau};
+            p.xy = pkfma(t2, wv.xy, p.xy);
+            p.zw = pkfma(t2, wv.zw, p.zw);
+        }
+        return p;
+    };
     // Per pair of obstacles: e = 1 + dx² + dy² (= 2·den), u = rcp(e); the potential's constants are
     // applied once at the end: cost = 0.8/den = 1.6·Σu, ∂cost/∂f = −0.8·d/den² = −3.2·Σ d·u².
     auto potential = [&](float x, float y, float& cv, float& ax, float& ay) {
@@ -326,7 +343,9 @@ __device__ __forceinline__ void eval_waypoint(const KParams& P, const float (&q)
             f32x2 dx[6], dy[6], u[6];
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
-                const f32x4 p = oreg ? oreg[i] : o4[i];
+                f32x4 p;
+                if constexpr (MOVING) p = pair_at(i);
+                else p = oreg ? oreg[i] : o4[i];
                 dx[i] = fx2 - p.xy;
                 dy[i] = fy2 - p.zw;
                 const f32x2 e = pkfma(dy[i], dy[i], pkfma(dx[i], dx[i], one));
@@ -345,7 +364,14 @@ __device__ __forceinline__ void eval_waypoint(const KParams& P, const float (&q)
             }
         } else {
             for (int c = 0; c < nq; ++c) {
-                const f32x4 p0 = o4[2 * c], p1 = o4[2 * c + 1];
+                f32x4 p0, p1;
+                if constexpr (MOVING) {
+                    p0 = pair_at(2 * c);
+                    p1 = pair_at(2 * c + 1);
+                } else {
+                    p0 = o4[2 * c];
+                    p1 = o4[2 * c + 1];
+                }
                 pair2(p0.xy, p0.zw);
                 pair2(p1.xy, p1.zw);
             }
@@ -455,9 +481,16 @@ __device__ __forceinline__ void potential_pair(const KParams& P, const float* __
 }
 
 // eval_waypoint with the cost variant chosen at run time (host-API kernels, DynShape optimiser).
+// vel / tau: the moving variant (P.moving; vel the LDS velocity table behind ob's, tau the lane's time)
 template <int D>
 __device__ __forceinline__ void eval_waypoint_rt(const KParams& P, const float (&q)[D], const float (&v)[D],
-                                                 const float* __restrict__ ob, WP<D>& w) {
+                                                 const float* __restrict__ ob, WP<D>& w,
+                                                 const float* __restrict__ vel = nullptr, float tau = 0.f) {
+    if (P.moving) {
+        if (P.whole_robot) eval_waypoint<D, true, true, false, true>(P, q, v, ob, w, nullptr, vel, tau);
+        else eval_waypoint<D, false, true, false, true>(P, q, v, ob, w, nullptr, vel, tau);
+        return;
+    }
     if (P.whole_robot) eval_waypoint<D, true>(P, q, v, ob, w);
     else eval_waypoint<D, false>(P, q, v, ob, w);
 }
@@ -620,6 +653,11 @@ __device__ __forceinline__ EvalOut eval_finalize(const KParams& P, const float* 
 // Obstacles into LDS: one shared set (obs_stride 0) or one per trajectory,
 // each padded to obs_pitch floats with zero-contribution sentinels.
 __host__ __device__ inline int obs_pitch(int O) { return ((O + 3) & ~3) * 2; }
+// MOVING (the kernels that have the moving variant): a moving launch (P.moving) stages the velocity table
+// behind the positions (obs_vel_offset), in the same layout and from the same shared / per-problem indexing,
+// sentinels at velocity 0.
+__host__ __device__ inline int obs_vel_offset(const KParams& P) { return (P.obs_stride ? P.TB : 1) * obs_pitch(P.O); }
+template <bool MOVING = false>
 __device__ inline void stage_obstacles(const KParams& P, int tb0, int ntb, float* obsL) {
     const int pitch = obs_pitch(P.O), nsets = P.obs_stride ? P.TB : 1;
     for (int e = threadIdx.x; e < nsets * pitch; e += P.BT) {
@@ -633,6 +671,20 @@ __device__ inline void stage_obstacles(const KParams& P, int tb0, int ntb, float
             else if (tt < ntb) val = P.obstacles[(size_t)(tb0 + tt) * P.obs_stride + src];
         }
         obsL[e] = val;
+    }
+    if constexpr (!MOVING) return;
+    if (!P.moving) return;
+    float* velL = obsL + nsets * pitch;
+    for (int e = threadIdx.x; e < nsets * pitch; e += P.BT) {
+        const int tt = e / pitch, r = e - tt * pitch;
+        const int o = 2 * (r >> 2) + (r & 1), coord = (r >> 1) & 1;
+        float val = 0.f;
+        if (o < P.O) {
+            const int src = 2 * o + coord;
+            if (!P.obs_stride) val = P.obs_vel[src];
+            else if (tt < ntb) val = P.obs_vel[(size_t)(tb0 + tt) * P.obs_stride + src];
+        }
+        velL[e] = val;
     }
 }
 
@@ -1127,7 +1179,9 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
 
     // ----------------------------------------------------------- prologue
     if (OPS_LDS && !REGOPS) {
-        const Plan L = plan_lds(P, OPS_LDS, true);
+        bool mov = false;  // (only the DynShape instantiations have the moving variant)
+        if constexpr (S::kVariants) mov = P.moving != 0;
+        const Plan L = plan_lds(P, OPS_LDS, true, false, mov);
         const int n1 = (int)frag_floats(RP, MP) / 4, n2 = (int)frag_floats(MP, RP) / 4;
         const f32x4* g1 = reinterpret_cast<const f32x4*>(P.F1frag);
         const f32x4* g2 = reinterpret_cast<const f32x4*>(P.F2frag);
@@ -1169,7 +1223,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
     const float h0V = valid ? P.Hend[NK + n] : 0.f, h1V = valid ? P.Hend[MP + NK + n] : 0.f;
     const float fb0 = yrow ? P.Fbot[(size_t)0 * RP + n] : 0.f;
     const float fb1 = yrow ? P.Fbot[(size_t)(N - 1) * RP + n] : 0.f;
-    stage_obstacles(P, tb0, ntb, obsL);
+    stage_obstacles<S::kVariants>(P, tb0, ntb, obsL);
     for (int e = tid; e < RP * kLd; e += P.BT) Ymix[e] = 0.f;
     // GD: the rounding residual rows e' live in dP's direction columns between an accepted step and the
     // next stage 1 (stage 2 rewrites dP only after the stage-1 barrier); none pending at start
@@ -1238,6 +1292,16 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
     __syncthreads();  // every lane has read α0 from X
     for (int e = tid; e < MP * kLd; e += P.BT) X[e] = 0.f;
     const float* obs = obsL + (P.obs_stride ? t * obs_pitch(P.O) : 0);
+    // moving obstacles (DynShape launches only, launch_optimize): the velocity table behind the positions and
+    // this lane's support time t[n]
+    const float* obsv = obs;
+    float tau = 0.f;
+    if constexpr (S::kVariants) {
+        if (P.moving) {
+            obsv = obs + obs_vel_offset(P);
+            tau = valid ? P.tsup[n] : 0.f;
+        }
+    }
 
     // stage 1 over the units of this wave: Ypart[s] = Fᵀ·[a'; b'] (velocity half if `full`)
     auto stage1 = [&](bool full) {
@@ -1691,7 +1755,10 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
         if (ev) {
             if (valid) {
                 if constexpr (S::kVariants) {
-                    if (P.whole_robot) eval_waypoint<D, true, true, true>(P, q2, v2, obs, w);
+                    if (P.moving) {  // this waypoint's obstacle table is the one at its support time
+                        if (P.whole_robot) eval_waypoint<D, true, true, true, true>(P, q2, v2, obs, w, nullptr, obsv, tau);
+                        else eval_waypoint<D, false, true, true, true>(P, q2, v2, obs, w, nullptr, obsv, tau);
+                    } else if (P.whole_robot) eval_waypoint<D, true, true, true>(P, q2, v2, obs, w);
                     else eval_waypoint<D, false, true, true>(P, q2, v2, obs, w);
                 } else {
                     eval_waypoint<D, false, true, true>(P, q2, v2, obs, w);
@@ -4344,7 +4411,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
 template <int D, int MAXT>
 __global__ __launch_bounds__(MAXT) void k_forward(KParams P, int mode) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const Plan L = plan_lds(P, false, false);
+    const Plan L = plan_lds(P, false, false, false, P.moving != 0);
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int N = P.N, NW = P.NW, TB = P.TB, MP = P.MP;
@@ -4362,7 +4429,7 @@ __global__ __launch_bounds__(MAXT) void k_forward(KParams P, int mode) {
     float* sg = smem + L.sg;
     float* obsL = smem + L.obs;
 
-    stage_obstacles(P, tb0, ntb, obsL);
+    stage_obstacles<true>(P, tb0, ntb, obsL);
     stage_alpha<D>(P, tb0, ntb, XG, MP);
     __syncthreads();
     float q[D], v[D], s[D], g[D];
@@ -4383,7 +4450,8 @@ __global__ __launch_bounds__(MAXT) void k_forward(KParams P, int mode) {
     }
     WP<D> w;
     if (tvalid) {
-        if (valid) eval_waypoint_rt<D>(P, q, v, obsL, w);
+        // (obstacles: shared only here, obs_stride 0 — the velocity table follows the one position table)
+        if (valid) eval_waypoint_rt<D>(P, q, v, obsL, w, obsL + obs_vel_offset(P), P.moving ? P.tsup[n] : 0.f);
         eval_partials<D>(P, valid, w, n, wave, q, v, s, g, red, sg, t);
     }
     __syncthreads();
@@ -4691,7 +4759,7 @@ hipError_t launch_dense_shape(const KParams& p, hipStream_t s, LaunchDesc* desc,
 template <class Sh>
 hipError_t launch_general_shape(const KParams& p, hipStream_t s, LaunchDesc* desc) {
     const bool stage = p.ops_in_lds != 0;
-    const Plan L = plan_lds(p, stage, true);
+    const Plan L = plan_lds(p, stage, true, false, Sh::kVariants && p.moving != 0);
     const size_t lds = (size_t)L.total * 4;
     const int grid = (p.B + p.TB - 1) / p.TB;
     if (grid <= 0) return hipSuccess;
@@ -4734,7 +4802,7 @@ hipError_t launch_general_shape(const KParams& p, hipStream_t s, LaunchDesc* des
 
 template <int D>
 hipError_t launch_forward_dim(const KParams& p, int mode, hipStream_t s) {
-    const Plan L = plan_lds(p, false, false);
+    const Plan L = plan_lds(p, false, false, false, p.moving != 0);
     const size_t lds = (size_t)L.total * 4;
     const int grid = (p.B + p.TB - 1) / p.TB;
     if (grid <= 0) return hipSuccess;

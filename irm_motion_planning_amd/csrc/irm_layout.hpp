@@ -111,6 +111,14 @@ struct KParams {
     int32_t queue_groups;
     int32_t num_cus;
     int32_t* queue;
+    // moving obstacles (irm_*_moving): obstacle o of a waypoint at plan time τ is at fmaf(τ, w, p).  Appended
+    // here so that no earlier kernarg offset moves.  obs_vel: the velocity table, the shape and stride of
+    // `obstacles`; tsup: the lanes' times on the device — the support times t[n] (uploaded once per
+    // context), or the evaluation times of irm_dense_check; moving: the launch reads them (and the LDS
+    // layout holds a second obstacle table, plan_lds)
+    const float* obs_vel;
+    const float* tsup;
+    int32_t moving;
 };
 
 constexpr int kTraceW = 10;  // outer, inner, trial, lr, new_loss, required_loss, accepted, loss, ‖g‖, alpha_norm
@@ -212,7 +220,11 @@ __host__ __device__ constexpr Head plan_head(int MP, int RP, int nsplit, bool op
     return H;
 }
 
-__host__ __device__ inline Plan plan_lds(const KParams& p, bool ops_lds, bool optimizer, bool lean = false) {
+// moving: the launch stages the obstacles' velocity table behind the positions — twice the obstacle words.
+// (An argument, not a read of p.moving: the callers that can run a moving launch pass it, and the code of the
+// kernels without the variant stays as it is.)
+__host__ __device__ inline Plan plan_lds(const KParams& p, bool ops_lds, bool optimizer, bool lean = false,
+                                         bool moving = false) {
     const Head H = plan_head(p.MP, p.RP, p.nsplit, optimizer, lean);
     Plan L{};
     L.X = H.X;
@@ -226,7 +238,7 @@ __host__ __device__ inline Plan plan_lds(const KParams& p, bool ops_lds, bool op
     L.wp = H.wp;
     L.flags = H.flags;
     L.obs = H.obs;
-    int off = H.obs + al4((p.obs_stride ? p.TB : 1) * ((p.O + 3) & ~3) * 2 + 4);
+    int off = H.obs + al4((moving ? 2 : 1) * (p.obs_stride ? p.TB : 1) * ((p.O + 3) & ~3) * 2 + 4);
     L.f1 = L.f2 = 0;
     if (optimizer && ops_lds && !p.regops) {  // with REGOPS the A-fragments live in VGPRs
         L.f1 = off;

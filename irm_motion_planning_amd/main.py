@@ -8,8 +8,9 @@ files trajectory_result.txt / trajectory_series.txt (np.savetxt defaults).
 
 Additive flags (no reference counterpart): --batch-size, --seed,
 --operator-rank, --device, --whole-robot-cost, --work-queue, --dense-check
-(which adds one stdout line and trajectory_result_dense.txt) and
---coarse-n-timesteps (coarse-to-fine: two stdout lines per optimize()).
+(which adds one stdout line and trajectory_result_dense.txt),
+--coarse-n-timesteps (coarse-to-fine: two stdout lines per optimize()) and
+--obstacle-velocity (obstacles that drift at a constant velocity over the plan).
 """
 import argparse
 import os
@@ -133,6 +134,10 @@ def build_parser():
                         help="Coarse-to-fine: optimise on Nc support times first, carry that solution onto the "
                              "--n-timesteps grid (transfer_alpha) and optimise from it; the output files are the "
                              "fine stage's (default: 0 = off)")
+    parser.add_argument('--obstacle-velocity', type=float, nargs=2, default=None, metavar=('VX', 'VY'),
+                        help="Every obstacle of every problem drifts by (VX, VY) over the plan (t in [0, 1]): the "
+                             "optimiser and --dense-check see obstacle o at p + t*(VX, VY) at plan time t "
+                             "(default: absent = static obstacles)")
     return parser
 
 
@@ -173,13 +178,13 @@ def print_stages(stages):
               len(st["constraints_ok"]), ", final loss mean", float(np.mean(st["final_loss"])))
 
 
-def dense_report(context, alpha, obstacles, M):
+def dense_report(context, alpha, obstacles, M, obstacle_velocity=None):
     """--dense-check M: the result on linspace(0, 1, M).  Prints problem 0's line, writes its M×D positions
-    and returns the batch's report (Context.dense_check)."""
+    and returns the batch's report (Context.dense_check; obstacle_velocity: the --obstacle-velocity table)."""
     t = np.linspace(0, 1, M, dtype=np.float32)
     context.set_eval_times(t)
     alpha = np.asarray(alpha, np.float32)
-    rep = context.dense_check(alpha, obstacles)
+    rep = context.dense_check(alpha, obstacles, obstacle_velocity=obstacle_velocity)
     first = {k: (v if alpha.ndim == 2 else v[0]) for k, v in rep.items()}
     f32 = np.float32
     print(f"dense check ({M} samples): max cost", f32(first["max_cost"]), "at t=" + str(t[int(first["argmax_cost"])]) + ";",
@@ -262,7 +267,7 @@ def run_batch(optimizer, args):
     ok0 = tr.constraintsFulfilledVerbose(alpha[0], start[0], goal[0], verbose=True)
     print("result cost: ( avg", avg[0], ", max", mx[0], "). constraint fulfiled", ok0)
     if getattr(args, "dense_check", 0) > 0:
-        rep = dense_report(optimizer.context, alpha, env.obstacles, args.dense_check)
+        rep = dense_report(optimizer.context, alpha, env.obstacles, args.dense_check, optimizer.obstacle_velocity)
         dense_ok = rep["position_ok"] & rep["velocity_ok"]
         print("dense check:", int(np.sum(np.asarray(ok, bool) & ~dense_ok)), "of", int(np.sum(ok)),
               "problems that fulfil the constraints on the support grid exceed a joint or velocity limit between "
@@ -348,7 +353,7 @@ def main(argv=None):
     np_trajectory = np.array(tr.evaluate(result_alpha, tr.km, tr.jac))
     np.savetxt("trajectory_result.txt", np_trajectory)
     if args.dense_check > 0:
-        dense_report(optimizer.context, result_alpha, env.obstacles, args.dense_check)
+        dense_report(optimizer.context, result_alpha, env.obstacles, args.dense_check, optimizer.obstacle_velocity)
     if args.extended_vis:
         p_np = np.array(p)
         print(p_np.shape)

@@ -18,6 +18,10 @@ straight line of initTrajectory (optimizer_BLS.py:57-62).
   plan's configuration at tau the new start (irm_transfer_alpha_dev), so a robot that has executed part
   of its plan warm-starts the next one from where it is.
 
+* plan(..., obstacle_velocity=w) plans against obstacles that drift at a constant velocity over the
+  plan (waypoint n sees obstacle o at p + t[n]·w); the velocity table lives on the device next to the
+  obstacle table, and advance(tau) moves both to the new plan's time origin (advance_obstacles).
+
 The first call, or warm_start=False, is exactly Optimizer.optimize() for the batch.
 A warm-started call equals irm_optimize_batch with alpha0 = the previous α_out bit for
 bit (tests/test_gpu_parity.py::test_replanner_*).
@@ -27,6 +31,21 @@ import numpy as np
 from ._abi import STATS_FIELDS, IrmError
 from .context import Context, batch_dev
 from .params import params_from_args
+
+
+def advance_obstacles(p, w, tau):
+    """Obstacle tables of the plan that starts at plan time tau of the current one (Replanner.advance).
+
+    In fp32, with tau rounded to fp32 and c = fl(1 − tau):
+        p' = fl(p + fl(tau·w))      where each obstacle is at the old plan's time tau
+        w' = fl(c·w)                the remaining motion is stretched to unit time
+    so that an obstacle's position at the new plan's time s, p' + s·w', is its old position at
+    tau + (1 − tau)·s.  Two roundings per element, no fused multiply-add.  Returns (p', w')."""
+    p, w = np.asarray(p, np.float32), np.asarray(w, np.float32)
+    tau = np.float32(tau)
+    c = np.float32(1.0) - tau
+    step = (tau * w).astype(np.float32)
+    return (p + step).astype(np.float32), (c * w).astype(np.float32)
 
 
 class Replanner:
@@ -45,6 +64,9 @@ class Replanner:
         self.start = torch.zeros((B, D), **f32)
         self.goal = torch.zeros((B, D), **f32)
         self.obstacles = torch.zeros(((B if self.per_problem else 1) * max(O, 1), 2), **f32)
+        self.velocity = torch.zeros_like(self.obstacles)  # the obstacles' velocities (plan(obstacle_velocity=…))
+        self.moving = False       # did the latest plan have velocities?
+        self._have_obs = False    # is there a stored obstacle table (plan(obstacles=None))?
         self._alpha = [torch.zeros((B, N, D), **f32), torch.zeros((B, N, D), **f32)]
         self.traj = torch.zeros((B, N, D), **f32)
         self.stats = torch.zeros((B, len(STATS_FIELDS)), dtype=torch.int32, device=self.device)
@@ -57,32 +79,53 @@ class Replanner:
         x = np.array(np.broadcast_to(np.asarray(x, np.float32), shape))  # writable copy
         dst.copy_(self.torch.from_numpy(x).reshape(dst.shape), non_blocking=False)
 
-    def plan(self, obstacles, start=None, goal=None, warm_start=True, stream=None):
+    def plan(self, obstacles=None, start=None, goal=None, warm_start=True, stream=None, obstacle_velocity=None):
         """Optimise the batch against `obstacles` (O×2, or B×O×2 per problem).
 
-        start / goal (B×D or D) are kept from the previous call when None.  Returns
-        the per-problem statistics (dict of numpy arrays, irm_stats fields); the plan
+        start / goal (B×D or D) are kept from the previous call when None.  obstacles=None re-uses the
+        stored table (as advance() left it; an IrmError on the first call) and, unless obstacle_velocity
+        is given, the stored velocities; passing obstacles overrides the stored table, as fresh perception
+        would, and then the obstacles are static unless obstacle_velocity (the obstacles' shape) says
+        otherwise.  Returns the per-problem statistics (dict of numpy arrays, irm_stats fields); the plan
         stays on the device (alpha(), trajectory())."""
         torch = self.torch
         B, D, O = self.B, self.D, self.O
-        obs = np.asarray(obstacles, np.float32)
         want = (B, O, 2) if self.per_problem else (O, 2)
-        if obs.shape != want:
-            raise IrmError(f"obstacles must have shape {want}, got {obs.shape}")
+        if obstacles is None:
+            if not self._have_obs:
+                raise IrmError("the first plan() needs obstacles")
+            obs = None
+        else:
+            obs = np.asarray(obstacles, np.float32)
+            if obs.shape != want:
+                raise IrmError(f"obstacles must have shape {want}, got {obs.shape}")
+        vel = None
+        if obstacle_velocity is not None:
+            vel = np.asarray(obstacle_velocity, np.float32)
+            if vel.shape != want:
+                raise IrmError(f"obstacle_velocity must have shape {want}, got {vel.shape}")
+            if not np.all(np.isfinite(vel)):
+                raise IrmError("obstacle_velocity must be finite")
         if start is not None:
             self._put(self.start, start, (B, D))
         if goal is not None:
             self._put(self.goal, goal, (B, D))
         if self.calls == 0 and (start is None or goal is None):
             raise IrmError("the first plan() needs start and goal")
-        if O:
+        if O and obs is not None:
             self._put(self.obstacles, obs.reshape(-1, 2), self.obstacles.shape)
+        if O and vel is not None:
+            self._put(self.velocity, vel.reshape(-1, 2), self.velocity.shape)
+        if vel is not None or obs is not None:
+            self.moving = vel is not None and O > 0
+        self._have_obs = True
         warm = bool(warm_start) and self.planned
         a_in, a_out = self._alpha[self.cur], self._alpha[self.cur ^ 1]
         bd = batch_dev(alpha0=a_in.data_ptr() if warm else 0, start=self.start.data_ptr(),
                        goal=self.goal.data_ptr(), obstacles=self.obstacles.data_ptr(), n_obstacles=O,
                        obstacle_stride=2 * O if self.per_problem else 0, batch=B, alpha_out=a_out.data_ptr(),
-                       traj_out=self.traj.data_ptr(), stats_out=self.stats.data_ptr())
+                       traj_out=self.traj.data_ptr(), stats_out=self.stats.data_ptr(),
+                       obstacle_velocity=self.velocity.data_ptr() if self.moving else 0)
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
         self.context.optimize_dev(bd, s.cuda_stream)
         self.cur ^= 1
@@ -105,7 +148,14 @@ class Replanner:
 
         The remaining duration is stretched to unit time: velocities in the new parametrisation are
         (1 − tau) times the old ones (a plan that kept the velocity limit keeps it).  trajectory() and
-        the statistics still describe the plan before the advance until the next plan()."""
+        the statistics still describe the plan before the advance until the next plan().
+
+        Where the latest plan had obstacle velocities, world time stays consistent: the stored tables
+        become, in fp32 with c = fl(1 − tau),
+            p' = fl(p + fl(tau·w)),   w' = fl(c·w)
+        (advance_obstacles: the obstacles where they are at the old plan's time tau, their remaining
+        motion stretched to unit time), so plan() with obstacles=None continues against the same moving
+        scene.  Both updates are enqueued on `stream` with the transfer; nothing leaves HBM."""
         if not self.planned:
             raise IrmError("advance() needs a plan: call plan() first")
         tau = float(tau)
@@ -116,6 +166,12 @@ class Replanner:
         a_in, a_out = self._alpha[self.cur], self._alpha[self.cur ^ 1]
         self.context.transfer_alpha_dev(a_in.data_ptr(), self.B, a_out.data_ptr(), self.start.data_ptr(), s.cuda_stream)
         self.cur ^= 1
+        if self.moving:
+            t32 = np.float32(tau)
+            c32 = np.float32(1.0) - t32
+            with self.torch.cuda.stream(s):  # (separate multiply and add: two roundings, as advance_obstacles)
+                self.obstacles.add_(self.velocity * float(t32))
+                self.velocity.mul_(float(c32))
 
     def alpha(self):
         """The latest plan's α (B×N×D, device tensor)."""

@@ -1,0 +1,330 @@
+"""Moving obstacles on the GPU: every obstacle has a velocity, and the table a waypoint sees is the table at
+that waypoint's time (include/irm.h, "Moving obstacles").
+
+The yardstick is the fp64 restatement of tests/moving_cases.py (checked on the CPU by
+tests/test_moving_host.py) plus bit-identity: a zero velocity changes nothing, and dense_check at time τ is
+the static dense_check against the table frozen at p + τ·w.  Shapes: N = 33 (DynShape, support times n/32
+exact in fp32), N = 64 at D = 3 (a shape the static dispatch gives to k_lean), D = 7 at N = 40;
+O ∈ {5, 11, 13} (the 9-12-obstacle block, the pair loop, sentinel padding); B = 6 (a ragged last workgroup).
+"""
+import numpy as np
+import pytest
+
+import moving_cases as mc
+from conftest import GOAL, START, params, ref_args
+
+pytestmark = pytest.mark.gpu
+
+ORACLE_FLOOR = 5e-3  # the project's band floor for device-vs-restatement iterates (tests/test_gpu_parity.py)
+GD = ("--optimizer-name", "gd", "--max-outer-iteration", "1", "--loop-loss-reduction=-1e30")
+GD20 = GD + ("--max-inner-iteration", "20")
+BLS1 = ("--optimizer-name", "bls", "--max-outer-iteration", "1", "--max-inner-iteration", "10")
+
+
+def ctx(*argv, **overrides):
+    from irm_motion_planning_amd.context import Context
+    return Context(params(*argv, **overrides))
+
+
+def problems(B, D, seed):
+    rng = np.random.default_rng(seed)
+    return (rng.uniform(-0.5, 0.5, (B, D)).astype(np.float32), rng.uniform(0.2, 1.6, (B, D)).astype(np.float32))
+
+
+def assert_same_run(x, y):
+    """(alpha, traj, stats) of two optimize() calls, bit for bit, every irm_stats field."""
+    np.testing.assert_array_equal(x[0], y[0])
+    np.testing.assert_array_equal(x[1], y[1])
+    assert set(x[2]) == set(y[2])
+    for k in x[2]:
+        np.testing.assert_array_equal(x[2][k], y[2][k], err_msg=k)
+
+
+def assert_same_report(x, y):
+    assert set(x) == set(y)
+    for k in x:
+        np.testing.assert_array_equal(x[k], y[k], err_msg=k)
+
+
+# ------------------------------------------------------------------ 1. zero velocity changes nothing
+@pytest.mark.parametrize("per_problem", [False, True], ids=["shared", "per-problem"])
+@pytest.mark.parametrize("whole", [0, 1], ids=["ee", "whole"])
+@pytest.mark.parametrize("O", [5, 11, 13])
+def test_zero_velocity_changes_nothing(O, whole, per_problem):
+    B, N, D = 6, 33, 3
+    s, g = problems(B, D, 11 + O)
+    p, _ = mc.crossing_tables(B, O, 3.0, seed=O)
+    obs = p if per_problem else p[0]
+    zero = np.zeros_like(obs)
+    shape = mc.shape_argv(N, D)
+    c = ctx(*GD20, *shape, whole_robot_cost=whole)
+    a0 = c.init_alpha(s, g)
+    for lam in ((0.5, 0.1, 0.5), (0.0, 0.0, 0.0), (50, 10, 1.0)):  # cost / gradient: one shared table
+        np.testing.assert_array_equal(c.eval_cost(a0, p[0], s, g, *lam, obstacle_velocity=zero.reshape(-1, O, 2)[0]),
+                                      c.eval_cost(a0, p[0], s, g, *lam))
+        Gm, cm = c.eval_cost_grad(a0, p[0], s, g, *lam, with_cost=True, obstacle_velocity=np.zeros((O, 2), np.float32))
+        Gs, cs = c.eval_cost_grad(a0, p[0], s, g, *lam, with_cost=True)
+        np.testing.assert_array_equal(Gm, Gs)
+        np.testing.assert_array_equal(cm, cs)
+    static = c.optimize(s, g, obs)
+    assert "k_optimize<DynShape<3>" in c.launch_plan(B, O)["kernel"]  # both run DynShape here
+    assert_same_run(c.optimize(s, g, obs, obstacle_velocity=zero), static)
+    assert np.all(static[2]["grad_evals"] == 20)
+    cb = ctx(*BLS1, *shape, whole_robot_cost=whole)
+    assert_same_run(cb.optimize(s, g, obs, obstacle_velocity=zero), cb.optimize(s, g, obs))
+    c.set_eval_times(np.linspace(-0.125, 1.125, 41, dtype=np.float32))
+    assert_same_report(c.dense_check(static[0], obs, with_cost=True, obstacle_velocity=zero),
+                       c.dense_check(static[0], obs, with_cost=True))
+
+
+# ------------------------------------------------------------------ 2. dense_check against frozen tables
+@pytest.mark.parametrize("whole", [0, 1], ids=["ee", "whole"])
+@pytest.mark.parametrize("O", [5, 11, 13])
+def test_dense_check_equals_frozen_tables(O, whole):
+    """Dyadic inputs: p + t_eval[i]·w is exact in fp32, so sample i of the moving check is sample i of the static
+    check against that frozen table, to the bit (M static launches)."""
+    B, N, D, M = 3, 33, 3, 24
+    c = ctx(*mc.shape_argv(N, D), whole_robot_cost=whole)
+    s, g = problems(B, D, 5)
+    rng = np.random.default_rng(77 + O)
+    alpha = (c.init_alpha(s, g) + 0.05 * rng.standard_normal((B, N, D))).astype(np.float32)
+    p, w = mc.dyadic_scene(O, B=B)
+    t = (rng.permutation(np.arange(-16, 81))[:M] / 64.0).astype(np.float32)  # multiples of 1/64 in [−0.25, 1.25]
+    t[:3] = (-0.25, 1.25, 0.5)
+    assert np.sum((t < 0) | (t > 1)) >= 2
+    c.set_eval_times(t)
+    mov = c.dense_check(alpha, p, with_cost=True, obstacle_velocity=w)
+    for i in range(M):
+        frozen = (p + t[i] * w).astype(np.float32)
+        np.testing.assert_array_equal(frozen.astype(np.float64), p.astype(np.float64) + float(t[i]) * w.astype(np.float64))
+        fro = c.dense_check(alpha, frozen, with_cost=True)
+        np.testing.assert_array_equal(mov["cost"][:, i], fro["cost"][:, i], err_msg=str(i))
+    for b in range(B):
+        cost = mov["cost"][b]
+        assert mov["max_cost"][b] == cost.max() and mov["argmax_cost"][b] == int(np.argmax(cost))
+        mean = cost.astype(np.float64).mean()
+        assert abs(float(mov["avg_cost"][b]) - mean) <= 1e-5 * abs(mean)
+    # the kinematic half of the report does not see the obstacles
+    sta = c.dense_check(alpha, p)
+    for k in ("max_position", "min_position", "max_abs_velocity", "argmax_abs_velocity", "position_ok", "velocity_ok"):
+        np.testing.assert_array_equal(mov[k], sta[k], err_msg=k)
+    # one shared table
+    one = c.dense_check(alpha, p[1], with_cost=True, obstacle_velocity=w[1])
+    np.testing.assert_array_equal(one["cost"][1], mov["cost"][1])
+
+
+# ------------------------------------------------------------------ 3. cost and gradient, non-zero velocities
+@pytest.mark.parametrize("lmax", [0.0, 0.25])
+@pytest.mark.parametrize("N,D,whole", [(33, 3, 0), (64, 3, 0), (40, 7, 0), (33, 3, 1)])
+def test_cost_and_grad_match_the_restatement(N, D, whole, lmax):
+    """Bounds of test_whole_robot_cost_and_grad for a well-conditioned α: cost 1e-5 relative, gradient
+    2e-4·max|G|.  The static entry point meets them on the same α with w = 0 (else the input is wrong, not the
+    feature), and the case can tell the frozen table from the moving one."""
+    B, O = 3, 11
+    shape = mc.shape_argv(N, D)
+    c = ctx(*shape, whole_robot_cost=whole)
+    R, o = mc.restatement(*shape, whole_robot=bool(whole))
+    alpha, s, g = mc.well_conditioned_alpha(o, B, D, seed=N + D)
+    reach = float(sum(o.params.link_length[i] for i in range(D)))
+    p, w = mc.crossing_tables(B, O, 0.8 * reach, seed=N)  # per-problem tables: one call per problem
+    lam = (0.5, 0.1, lmax)
+    for b in range(B):
+        tab = R.table(p[b], w[b])
+        ref, Gref = R.cost(alpha[b], tab, s[b], g[b], *lam), R.cost_g(alpha[b], tab, s[b], g[b], *lam)
+        G, cost = c.eval_cost_grad(alpha[b], p[b], s[b], g[b], *lam, with_cost=True, obstacle_velocity=w[b])
+        assert cost == c.eval_cost(alpha[b], p[b], s[b], g[b], *lam, obstacle_velocity=w[b])
+        ref0, Gref0 = R.cost(alpha[b], p[b], s[b], g[b], *lam), R.cost_g(alpha[b], p[b], s[b], g[b], *lam)
+        G0, cost0 = c.eval_cost_grad(alpha[b], p[b], s[b], g[b], *lam, with_cost=True)
+        print(f"N={N} D={D} whole={whole} lmax={lmax} b={b}: moving cost {cost:.7f} vs {ref:.7f} (rel {abs(cost - ref) / abs(ref):.1e}), "
+              f"|G - ref| {np.abs(G - Gref).max() / np.abs(Gref).max():.1e}·max|G|; static rel {abs(cost0 - ref0) / abs(ref0):.1e}, "
+              f"{np.abs(G0 - Gref0).max() / np.abs(Gref0).max():.1e}")
+        assert abs(cost0 - ref0) <= 1e-5 * abs(ref0), "the input is wrong, not the feature"
+        assert np.abs(G0 - Gref0).max() <= 2e-4 * np.abs(Gref0).max(), "the input is wrong, not the feature"
+        assert abs(cost - ref) <= 1e-5 * abs(ref), (b, cost, ref)
+        assert np.abs(G - Gref).max() <= 2e-4 * np.abs(Gref).max(), b
+        assert abs(cost0 - cost) > 1e-3 * abs(cost), (cost0, cost)
+
+
+# ------------------------------------------------------------------ 4. a moving launch leaves k_lean
+@pytest.mark.parametrize("N", [64, 128])
+def test_moving_launch_runs_the_general_kernel(N):
+    c = ctx(*GD20, *mc.shape_argv(N, 3))
+    w = np.zeros((11, 2), np.float32)
+    for B in (6, 1024):
+        mov, sta = c.launch_plan(B, 11, obstacle_velocity=w), c.launch_plan(B, 11)
+        assert mov["lean"] == 0 and mov["kernel"].startswith("k_optimize<DynShape<3>"), mov
+        assert sta["lean"] == 1 and sta["kernel"].startswith("k_lean<"), sta
+    assert c.launch_plan(6, 0, obstacle_velocity=w)["lean"] == 1  # no obstacle, nothing moves: the static launch
+
+
+# ------------------------------------------------------------------ 5. GD iterates against the restatement
+@pytest.mark.parametrize("N", [33, 64])
+def test_gd_iterates_match_the_restatement(N):
+    """15 GD steps, λmax = 0.  The band is measured on the existing code path: e_static = max |static device run −
+    Ref64.gd_single| with the obstacles frozen at t = 0; the moving run lies within max(2·e_static, ORACLE_FLOOR)
+    of the moving restatement (the factor 2: the allowance for a second, equally rounded run)."""
+    B, D, O = 6, 3, 11
+    argv = GD + ("--max-inner-iteration", "15", "--lambda-max-cost", "0") + tuple(mc.shape_argv(N, D))
+    c = ctx(*argv)
+    R, o = mc.restatement(*argv)
+    s, g = problems(B, D, N)
+    p, w = mc.crossing_tables(B, O, 2.4, seed=N)
+    a0 = c.init_alpha(s, g)
+    _, t_sta, st_sta = c.optimize(s, g, p, alpha0=a0)
+    _, t_mov, st_mov = c.optimize(s, g, p, alpha0=a0, obstacle_velocity=w)
+    assert np.all(st_sta["grad_evals"] == 15) and np.all(st_mov["grad_evals"] == 15)
+    e_static = e_moving = 0.0
+    for b in range(B):
+        a_s, _, n_s = R.gd_single(a0[b], p[b], s[b], g[b], 15)
+        a_m, _, n_m = R.gd_single(a0[b], R.table(p[b], w[b]), s[b], g[b], 15)
+        assert n_s == n_m == 15
+        e_static = max(e_static, float(np.abs(t_sta[b] - R.traj_vel(a_s)[0]).max()))
+        e_moving = max(e_moving, float(np.abs(t_mov[b] - R.traj_vel(a_m)[0]).max()))
+    moved = float(np.abs(t_mov - t_sta).max())
+    print(f"N={N}: e_static {e_static:.3e}, moving error {e_moving:.3e}, band {max(2 * e_static, ORACLE_FLOOR):.3e}; "
+          f"|moving plan - static plan| {moved:.3e}")
+    assert e_moving <= max(2.0 * e_static, ORACLE_FLOOR), (e_moving, e_static)
+
+
+# ------------------------------------------------------------------ 6. the optimiser minimises the moving objective
+@pytest.mark.parametrize("flow", ["gd", "bls"])
+@pytest.mark.parametrize("N,D", [(33, 3), (40, 7)])
+def test_optimizer_minimises_the_moving_objective(N, D, flow):
+    B, O = 3, 11
+    argv = (GD20 if flow == "gd" else BLS1[:4]) + tuple(mc.shape_argv(N, D))
+    c = ctx(*argv)
+    pr = c.params
+    lam = (pr.lambda_sg_constraint, pr.lambda_jl_constraint, pr.lambda_max_cost)
+    s, g = problems(B, D, 3 * N)
+    reach = float(sum(pr.link_length[i] for i in range(D)))
+    p, w = mc.crossing_tables(1, O, 0.8 * reach, seed=D)
+    p, w = p[0], w[0]
+    a0 = c.init_alpha(s, g)
+    alpha, traj, st = c.optimize(s, g, p, alpha0=a0, obstacle_velocity=w)
+    final = st["final_loss"].astype(np.float64)
+    at_out = c.eval_cost(alpha, p, s, g, *lam, obstacle_velocity=w).astype(np.float64)
+    at_a0 = c.eval_cost(a0, p, s, g, *lam, obstacle_velocity=w).astype(np.float64)
+    static_out = c.eval_cost(alpha, p, s, g, *lam).astype(np.float64)
+    print(f"N={N} D={D} {flow}: final_loss {final}, moving cost of alpha_out {at_out}, of alpha0 {at_a0}, "
+          f"static cost of alpha_out {static_out}, grad evals {st['grad_evals']}")
+    assert np.all(np.abs(final - at_out) <= 1e-5 * np.abs(at_out)), (final, at_out)
+    assert np.all(final < at_a0)
+    assert np.all(np.abs(final - static_out) > 1e-3 * np.abs(static_out))
+    np.testing.assert_array_equal(traj, c.evaluate(alpha))
+
+
+# ------------------------------------------------------------------ 7. batch independence
+def test_moving_batch_rows_are_independent():
+    B, N, D, O = 6, 33, 3, 13
+    c = ctx(*GD20, *mc.shape_argv(N, D))
+    s, g = problems(B, D, 8)
+    p, w = mc.crossing_tables(B, O, 2.4, seed=8)
+    _, traj, _ = c.optimize(s, g, p, obstacle_velocity=w)
+    for b in range(B):
+        _, t1, _ = c.optimize(s[b], g[b], p[b], obstacle_velocity=w[b])
+        np.testing.assert_allclose(traj[b], t1, rtol=0, atol=1e-4)
+
+
+# ------------------------------------------------------------------ 8. the crossing scene
+def test_crossing_scene_plan_with_velocities_is_safer():
+    """The plan made with the velocities has a lower largest moving potential on 129 times than the plan made
+    against the table frozen at t = 0 (the CPU suite shows a margin of more than 10 % in fp64)."""
+    c = ctx(*mc.CROSSING_ARGV)
+    a_m, _, st_m = c.optimize(START, GOAL, mc.CROSSING_P, obstacle_velocity=mc.CROSSING_W)
+    a_f, _, st_f = c.optimize(START, GOAL, mc.CROSSING_P)
+    assert int(st_m["grad_evals"]) == int(st_f["grad_evals"]) == 200
+    c.set_eval_times(np.linspace(0, 1, mc.CROSSING_M, dtype=np.float32))
+    m = c.dense_check(a_m, mc.CROSSING_P, obstacle_velocity=mc.CROSSING_W)["max_cost"]
+    f = c.dense_check(a_f, mc.CROSSING_P, obstacle_velocity=mc.CROSSING_W)["max_cost"]
+    print(f"moving max_cost on 129 times: plan with velocities {float(m):.4f}, plan against the frozen table {float(f):.4f}")
+    assert float(m) < float(f)
+
+
+# ------------------------------------------------------------------ 9. Replanner
+@pytest.mark.parametrize("per_problem", [False, True], ids=["shared", "per-problem"])
+def test_replanner_moving(per_problem):
+    from irm_motion_planning_amd._abi import IrmError
+    from irm_motion_planning_amd.replanning import Replanner, advance_obstacles
+    argv = GD20 + tuple(mc.shape_argv(33, 3))
+    args = ref_args(*argv)
+    B, O, tau = 6, 11, 0.25
+    s, g = problems(B, 3, 41)
+    p, w = mc.dyadic_scene(O, B=B)
+    if not per_problem:
+        p, w = p[0], w[0]
+    rp = Replanner(args, batch=B, n_obstacles=O, per_problem_obstacles=per_problem)
+    with pytest.raises(IrmError):
+        rp.plan(None, s, g)  # no stored table yet
+    c = ctx(*argv)
+    st = rp.plan(p, s, g, obstacle_velocity=w)
+    a_h, t_h, st_h = c.optimize(s, g, p, obstacle_velocity=w)
+    np.testing.assert_array_equal(rp.alpha_host(), a_h)
+    np.testing.assert_array_equal(rp.trajectory_host(), t_h)
+    np.testing.assert_array_equal(st["final_loss"], st_h["final_loss"])
+    assert np.abs(t_h - c.optimize(s, g, p)[1]).max() > 1e-4  # the velocities reached the launch
+    rp.advance(tau)
+    rp.torch.cuda.synchronize()
+    p1, w1 = advance_obstacles(p, w, tau)
+    np.testing.assert_array_equal(rp.obstacles.cpu().numpy(), p1.reshape(-1, 2))
+    np.testing.assert_array_equal(rp.velocity.cpu().numpy(), w1.reshape(-1, 2))
+    c.set_transfer(33, t0=tau, t1=1.0)
+    a_t, start = c.transfer_alpha(a_h, with_start=True)
+    np.testing.assert_array_equal(rp.alpha_host(), a_t)
+    rp.plan()  # obstacles=None: the stored tables, the transferred α, the new start
+    a_w, t_w, _ = c.optimize(start, g, p1, alpha0=a_t, obstacle_velocity=w1)
+    np.testing.assert_array_equal(rp.alpha_host(), a_w)
+    np.testing.assert_array_equal(rp.trajectory_host(), t_w)
+    # fresh perception overrides the stored tables; without velocities the plan is the static one
+    rp.plan(p, warm_start=False)
+    np.testing.assert_array_equal(rp.trajectory_host(), c.optimize(start, g, p)[1])
+
+
+# ------------------------------------------------------------------ 10. CLI
+CLI = ["--optimizer-name", "gd", "--max-outer-iteration", "1", "--max-inner-iteration", "10", "--n-timesteps", "33",
+       "--dense-check", "17"]
+
+
+def test_cli_obstacle_velocity(tmp_path, monkeypatch):
+    from irm_motion_planning_amd import main as irm_main
+    files = ("trajectory_result.txt", irm_main.DENSE_RESULT)
+    out = {}
+    for tag, extra in (("none", []), ("zero", ["--obstacle-velocity", "0", "0"]),
+                       ("drift", ["--obstacle-velocity", "0.5", "-0.75"])):
+        d = tmp_path / tag
+        d.mkdir()
+        monkeypatch.chdir(d)
+        irm_main.main(CLI + extra)
+        out[tag] = {f: (d / f).read_bytes() for f in files}
+    for f in files:
+        assert out["zero"][f] == out["none"][f], f
+    assert out["drift"]["trajectory_result.txt"] != out["none"]["trajectory_result.txt"]
+    # batched path
+    for tag, extra in (("bnone", []), ("bzero", ["--obstacle-velocity", "0", "0"]), ("bdrift", ["--obstacle-velocity", "0.5", "-0.75"])):
+        d = tmp_path / tag
+        d.mkdir()
+        monkeypatch.chdir(d)
+        irm_main.main(CLI + ["--batch-size", "5"] + extra)
+        out[tag] = {f.name: f.read_bytes() for f in sorted(d.iterdir())}
+    assert out["bzero"] == out["bnone"] and len(out["bnone"]) >= 4
+    assert out["bdrift"]["trajectory_result_batch.txt"] != out["bnone"]["trajectory_result_batch.txt"]
+
+
+# ------------------------------------------------------------------ 11. validation
+def test_non_finite_velocity_is_refused():
+    from irm_motion_planning_amd._abi import IrmError
+    c = ctx(*GD20, *mc.shape_argv(33, 3))
+    s, g = problems(2, 3, 1)
+    p, w = mc.crossing_tables(2, 5, 2.0)
+    a0 = c.init_alpha(s, g)
+    c.set_eval_times([0.0, 0.5])
+    for bad in (np.nan, np.inf):
+        wb = w.copy()
+        wb[1, 3, 1] = bad
+        with pytest.raises(IrmError, match="not finite"):
+            c.optimize(s, g, p, obstacle_velocity=wb)
+        with pytest.raises(IrmError, match="not finite"):
+            c.dense_check(a0, p, obstacle_velocity=wb)
+        with pytest.raises(IrmError, match="not finite"):
+            c.eval_cost(a0, p[1], s, g, 0.5, 0.1, 0.5, obstacle_velocity=wb[1])
+    with pytest.raises(ValueError):
+        c.optimize(s, g, p, obstacle_velocity=w[0])  # the velocity table has the obstacles' shape
