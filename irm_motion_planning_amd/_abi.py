@@ -261,6 +261,35 @@ PROTOTYPES = {
     "irm_optimize_plan_moving": (
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(IrmLaunchPlan)]
     ),
+    # end-effector goals: the _moving twins' arguments plus goal_xy (B×2; NULL: the existing call), and the IK seed
+    "irm_eval_cost_task": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_float, ctypes.c_float, ctypes.c_float, c_float_p, c_float_p, c_float_p],
+    ),
+    "irm_eval_cost_grad_task": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_float, ctypes.c_float, ctypes.c_float, c_float_p, c_float_p, c_float_p, c_float_p],
+    ),
+    "irm_constraints_task": (
+        ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, c_uint8_p, c_float_p, c_float_p]
+    ),
+    "irm_optimize_batch_task": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, c_float_p, c_float_p, ctypes.POINTER(IrmStats), c_float_p, c_float_p, c_float_p],
+    ),
+    "irm_optimize_batch_task_dev": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IrmBatchDev), c_float_p, c_float_p, ctypes.c_void_p]
+    ),
+    "irm_optimize_plan_task": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(IrmLaunchPlan)]
+    ),
+    "irm_ik_seed": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, c_float_p, c_float_p]),
+    "irm_ik_seed_dev": (
+        ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, c_float_p, c_float_p, ctypes.c_void_p]
+    ),
     "irm_build_id": (ctypes.c_char_p, []),
     "irm_debug_phase_profile": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
     "irm_debug_bls_trace_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),

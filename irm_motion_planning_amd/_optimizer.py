@@ -43,6 +43,12 @@ class _PersistentOptimizer:
                                                      np.asarray(self.env.obstacles).shape).copy()
         self.trajectory = Trajectory(args, **overrides)
         self.context = self.trajectory.context
+        # --goal-xy X Y: the environment's problem is planned to that end-effector target; its goal
+        # configuration (the straight-line initialisation) becomes the IK seed from the start (None: joint goal)
+        self.goal_xy = None
+        if getattr(args, "goal_xy", None) is not None:
+            self.goal_xy = np.asarray(args.goal_xy, np.float32)
+            self.env.goal_config = self.context.ik_seed(self.env.start_config, self.goal_xy)[0]
         self.last_stats = None
         self.last_profile = {}
         t1 = time.time()
@@ -54,7 +60,8 @@ class _PersistentOptimizer:
     def optimize(self):
         t0 = time.perf_counter()
         res = self.context.optimize(self.env.start_config, self.env.goal_config, self.env.obstacles,
-                                    series=self.extendedVis, obstacle_velocity=self.obstacle_velocity)
+                                    series=self.extendedVis, obstacle_velocity=self.obstacle_velocity,
+                                    goal_xy=self.goal_xy)
         self.last_profile = {"optimize_ms": 1000 * (time.perf_counter() - t0)}
         if self.extendedVis:
             alpha, traj, stats, series = res
@@ -65,7 +72,7 @@ class _PersistentOptimizer:
         self.last_trajectory = traj
         return alpha
 
-    def coarse_to_fine(self, coarse, start, goal, obstacles=None, series=False):
+    def coarse_to_fine(self, coarse, start, goal, obstacles=None, series=False, goal_xy=None):
         """Coarse-to-fine optimize_batch(): solve the B problems on the support grid of `coarse` (a Context
         of the same hyper-parameters and another --n-timesteps), carry that solution onto this optimizer's
         grid (Context.set_transfer / transfer_alpha) and optimise from it.
@@ -77,17 +84,19 @@ class _PersistentOptimizer:
         D = self.trajectory.robot.N_joints
         start = np.asarray(start, np.float32).reshape(-1, D)
         goal = np.asarray(goal, np.float32).reshape(-1, D)
-        a_c, _, st_c = coarse.optimize(start, goal, obstacles, obstacle_velocity=vel)
+        a_c, _, st_c = coarse.optimize(start, goal, obstacles, obstacle_velocity=vel, goal_xy=goal_xy)
         self.context.set_transfer(coarse.N, rbf_variance_src=coarse.params.rbf_variance)
         alpha0 = self.context.transfer_alpha(a_c)
-        res = self.context.optimize(start, goal, obstacles, alpha0=alpha0, series=series, obstacle_velocity=vel)
+        res = self.context.optimize(start, goal, obstacles, alpha0=alpha0, series=series, obstacle_velocity=vel,
+                                    goal_xy=goal_xy)
         self.last_stats = res[2]
         self.last_stages = {"coarse": {"n_timesteps": coarse.N, "alpha": a_c, "stats": st_c},
                             "fine": {"n_timesteps": self.context.N, "alpha0": alpha0, "stats": res[2]}}
         return res
 
-    def optimize_batch(self, start, goal, obstacles=None, alpha0=None, obstacle_stride=0, series=False):
-        """Batched optimize(): B independent start/goal problems (B×D each).
+    def optimize_batch(self, start, goal, obstacles=None, alpha0=None, obstacle_stride=0, series=False, goal_xy=None):
+        """Batched optimize(): B independent start/goal problems (B×D each); goal_xy (B×2): end-effector
+        targets instead of the goal configurations (which then only shape the initial line).
 
         Returns (alpha, traj, stats) — plus the B × S × N × D snapshot buffer with
         series=True (stats["series_len"] frames valid per problem)."""
@@ -96,7 +105,7 @@ class _PersistentOptimizer:
         start = np.asarray(start, np.float32).reshape(-1, self.trajectory.robot.N_joints)
         goal = np.asarray(goal, np.float32).reshape(-1, self.trajectory.robot.N_joints)
         res = self.context.optimize(start, goal, obstacles, alpha0=alpha0, obstacle_stride=obstacle_stride,
-                                    series=series, obstacle_velocity=vel)
+                                    series=series, obstacle_velocity=vel, goal_xy=goal_xy)
         self.last_stats = res[2]
         return res
 

@@ -111,12 +111,15 @@ class Context:
         d["build_id"] = d["build_id"].decode()
         return d
 
-    def launch_plan(self, batch, n_obstacles=0, series=False, obstacle_velocity=None):
+    def launch_plan(self, batch, n_obstacles=0, series=False, obstacle_velocity=None, goal_xy=None):
         """The optimiser launch optimize() runs for `batch` problems (irm_optimize_plan: filled in by
         the library's own launch dispatch, nothing launched).  obstacle_velocity not None: the launch of
-        a moving call (irm_optimize_plan_moving; only whether it is given matters)."""
+        a moving call (irm_optimize_plan_moving; only whether it is given matters).  goal_xy not None: the
+        launch of an end-effector-goal call (irm_optimize_plan_task; the same general kernel)."""
         pl = IrmLaunchPlan()
         fn = self.lib.irm_optimize_plan if obstacle_velocity is None else self.lib.irm_optimize_plan_moving
+        if goal_xy is not None:
+            fn = self.lib.irm_optimize_plan_task
         check(fn(self._h, int(batch), int(n_obstacles), int(bool(series)), ctypes.byref(pl)))
         d = {name: getattr(pl, name) for name, _ in IrmLaunchPlan._fields_}
         d["kernel"] = d["kernel"].decode()
@@ -275,6 +278,11 @@ class Context:
         """Enqueue irm_fit_alpha_dev with raw device addresses (e.g. torch data_ptr())."""
         check(self.lib.irm_fit_alpha_dev(self._h, _dev(traj_dev), int(batch), _dev(alpha_dev), ctypes.c_void_p(stream)))
 
+    def ik_seed_dev(self, start_dev, goal_xy_dev, batch, q_dev, residual_dev=0, stream=0):
+        """Enqueue irm_ik_seed_dev with raw device addresses; residual_dev 0: no residual output."""
+        check(self.lib.irm_ik_seed_dev(self._h, _dev(start_dev), _dev(goal_xy_dev), int(batch), _dev(q_dev),
+                                       _dev(residual_dev), ctypes.c_void_p(stream)))
+
     def transfer_alpha_dev(self, alpha_src_dev, batch, alpha_dev, start_dev=0, stream=0):
         """Enqueue irm_transfer_alpha_dev with raw device addresses; start_dev 0: no start output."""
         check(self.lib.irm_transfer_alpha_dev(self._h, _dev(alpha_src_dev), int(batch), _dev(alpha_dev),
@@ -293,14 +301,41 @@ class Context:
             raise ValueError(f"obstacle_velocity must have the obstacles' shape {obs.shape}, got {vel.shape}")
         return vel
 
-    def eval_cost(self, alpha, obstacles, start, goal, lsg, ljl, lmax, obstacle_velocity=None):
-        """obstacle_velocity (O×2): waypoint n sees obstacle o at p + t[n]·w (irm_eval_cost_moving)."""
+    def _goal_xy(self, goal_xy, B):
+        """The end-effector targets of a task call: fp32 B×2 (one target broadcasts over the batch)."""
+        return _f32(np.broadcast_to(_f32(goal_xy), (B, 2)))
+
+    def ik_seed(self, start, goal_xy):
+        """A joint configuration whose end effector is at goal_xy ((B×)2), by damped least squares started at
+        `start` ((B×)D) (irm_ik_seed).  Returns (q, residual): residual = ‖f(q) − p‖; best effort — a target
+        out of reach or behind the joint limits keeps a residual."""
+        s, single = self._batch(start, (self.D,))
+        B = s.shape[0]
+        p = _f32(goal_xy)
+        if p.ndim == 2 and B == 1 and p.shape[0] > 1:  # one start, several targets
+            B = p.shape[0]
+            s = _f32(np.broadcast_to(s, (B, self.D)))
+            single = False
+        p = self._goal_xy(p, B)
+        q = np.zeros((B, self.D), np.float32)
+        res = np.zeros(B, np.float32)
+        check(self.lib.irm_ik_seed(self._h, _ptr(s), _ptr(p), B, _ptr(q), _ptr(res)))
+        return (q[0], res[0]) if single else (q, res)
+
+    def eval_cost(self, alpha, obstacles, start, goal, lsg, ljl, lmax, obstacle_velocity=None, goal_xy=None):
+        """obstacle_velocity (O×2): waypoint n sees obstacle o at p + t[n]·w (irm_eval_cost_moving).
+        goal_xy ((B×)2): row N−1 is held to that end-effector target instead of `goal` (irm_eval_cost_task)."""
         a, single = self._batch(alpha, (self.N, self.D))
         B = a.shape[0]
         s, g = self._sg(start, goal, B)
         obs = _f32(obstacles).reshape(-1, 2)
         out = np.zeros(B, np.float32)
-        if obstacle_velocity is None:
+        if goal_xy is not None:
+            vel = None if obstacle_velocity is None else self._velocity(_f32(obstacle_velocity).reshape(-1, 2), obs)
+            check(self.lib.irm_eval_cost_task(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
+                                              float(lsg), float(ljl), float(lmax), _ptr(out), _ptr(vel),
+                                              _ptr(self._goal_xy(goal_xy, B))))
+        elif obstacle_velocity is None:
             check(self.lib.irm_eval_cost(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
                                          float(lsg), float(ljl), float(lmax), _ptr(out)))
         else:
@@ -309,14 +344,20 @@ class Context:
                                                 float(lsg), float(ljl), float(lmax), _ptr(out), _ptr(vel)))
         return out[0] if single else out
 
-    def eval_cost_grad(self, alpha, obstacles, start, goal, lsg, ljl, lmax, with_cost=False, obstacle_velocity=None):
+    def eval_cost_grad(self, alpha, obstacles, start, goal, lsg, ljl, lmax, with_cost=False, obstacle_velocity=None,
+                       goal_xy=None):
         a, single = self._batch(alpha, (self.N, self.D))
         B = a.shape[0]
         s, g = self._sg(start, goal, B)
         obs = _f32(obstacles).reshape(-1, 2)
         grad = np.zeros_like(a)
         cost = np.zeros(B, np.float32)
-        if obstacle_velocity is None:
+        if goal_xy is not None:
+            vel = None if obstacle_velocity is None else self._velocity(_f32(obstacle_velocity).reshape(-1, 2), obs)
+            check(self.lib.irm_eval_cost_grad_task(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
+                                                   float(lsg), float(ljl), float(lmax), _ptr(grad), _ptr(cost),
+                                                   _ptr(vel), _ptr(self._goal_xy(goal_xy, B))))
+        elif obstacle_velocity is None:
             check(self.lib.irm_eval_cost_grad(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
                                               float(lsg), float(ljl), float(lmax), _ptr(grad), _ptr(cost)))
         else:
@@ -328,14 +369,21 @@ class Context:
             grad, cost = grad[0], cost[0]
         return (grad, cost) if with_cost else grad
 
-    def constraints(self, alpha, start, goal):
+    def constraints(self, alpha, start, goal, goal_xy=None):
+        """goal_xy ((B×)2): the goal-position check is ‖f(τ_{N−1}) − p‖ < eps_position and report[1] that
+        Cartesian distance (irm_constraints_task)."""
         a, single = self._batch(alpha, (self.N, self.D))
         B = a.shape[0]
         s, g = self._sg(start, goal, B)
         ok = np.zeros(B, np.uint8)
         rep = np.zeros((B, 11), np.float32)
-        check(self.lib.irm_constraints(self._h, _ptr(a), _ptr(s), _ptr(g), B,
-                                       ok.ctypes.data_as(_abi.c_uint8_p), _ptr(rep)))
+        if goal_xy is None:
+            check(self.lib.irm_constraints(self._h, _ptr(a), _ptr(s), _ptr(g), B,
+                                           ok.ctypes.data_as(_abi.c_uint8_p), _ptr(rep)))
+        else:
+            check(self.lib.irm_constraints_task(self._h, _ptr(a), _ptr(s), _ptr(g), B,
+                                                ok.ctypes.data_as(_abi.c_uint8_p), _ptr(rep),
+                                                _ptr(self._goal_xy(goal_xy, B))))
         if single:
             return bool(ok[0]), rep[0]
         return ok.astype(bool), rep
@@ -371,13 +419,24 @@ class Context:
             cg = None if cg is None else cg[0]
         return (cv, cg) if with_grad else cv
 
-    def optimize(self, start, goal, obstacles, alpha0=None, obstacle_stride=0, series=False, obstacle_velocity=None):
+    def optimize(self, start, goal, obstacles, alpha0=None, obstacle_stride=0, series=False, obstacle_velocity=None,
+                 goal_xy=None):
         """Batched Optimizer.optimize(): returns (alpha, traj, stats[, series]).
         obstacle_velocity (the shape of obstacles): the optimiser minimises the cost in which waypoint n
-        sees obstacle o at p + t[n]·w (irm_optimize_batch_moving)."""
+        sees obstacle o at p + t[n]·w (irm_optimize_batch_moving).
+        goal_xy ((B×)2): the end effector of row N−1 is held to that target instead of the joint configuration
+        `goal` (irm_optimize_batch_task); `goal` then feeds only the straight-line initialisation, and
+        goal=None means "seed it with ik_seed(start, goal_xy)"."""
         s, single = self._batch(start, (self.D,))
-        g, _ = self._batch(goal, (self.D,))
         B = s.shape[0]
+        gxy = None
+        if goal_xy is not None:
+            gxy = self._goal_xy(goal_xy, B)
+            if goal is None:
+                goal, _ = self.ik_seed(s, gxy)
+        elif goal is None:
+            raise ValueError("optimize() needs a goal configuration or a goal_xy")
+        g, _ = self._batch(goal, (self.D,))
         obs = _f32(obstacles)
         O = obs.shape[-2] if obs.size else 0
         if obs.ndim == 3:  # per-problem obstacles B × O × 2: one row of 2·O floats per problem
@@ -398,7 +457,12 @@ class Context:
         stats = (IrmStats * B)()
         cap = self.series_capacity() if series else 0
         ser = np.zeros((B, cap, self.N, self.D), np.float32) if series else None
-        if obstacle_velocity is None:
+        if gxy is not None:
+            vel = None if obstacle_velocity is None else self._velocity(obstacle_velocity, obs)
+            check(self.lib.irm_optimize_batch_task(self._h, _ptr(a0), _ptr(s), _ptr(g), _ptr(obs), O,
+                                                   int(obstacle_stride), B, _ptr(alpha), _ptr(traj), stats, _ptr(ser),
+                                                   _ptr(vel), _ptr(gxy)))
+        elif obstacle_velocity is None:
             check(self.lib.irm_optimize_batch(self._h, _ptr(a0), _ptr(s), _ptr(g), _ptr(obs), O, int(obstacle_stride),
                                               B, _ptr(alpha), _ptr(traj), stats, _ptr(ser)))
         else:
@@ -431,12 +495,16 @@ class Context:
             check(n)
         return out[: min(int(n_trials), n)]
 
-    def optimize_dev(self, batch_dev, stream=0, obstacle_velocity_dev=0):
+    def optimize_dev(self, batch_dev, stream=0, obstacle_velocity_dev=0, goal_xy_dev=0):
         """Enqueue irm_optimize_batch_dev with device pointers (IrmBatchDev).  obstacle_velocity_dev: the
         device address of the velocity table (the batch's n_obstacles / obstacle_stride), or the
-        `obstacle_velocity` that batch_dev() was given; 0: the static launch."""
+        `obstacle_velocity` that batch_dev() was given; 0: the static launch.  goal_xy_dev: the device address
+        of the end-effector targets (batch × 2, irm_optimize_batch_task_dev); 0: the joint goal."""
         vel = obstacle_velocity_dev or getattr(batch_dev, "obstacle_velocity", 0)
-        if not vel:
+        if goal_xy_dev:
+            check(self.lib.irm_optimize_batch_task_dev(self._h, ctypes.byref(batch_dev), _dev(vel) if vel else None,
+                                                       _dev(goal_xy_dev), ctypes.c_void_p(stream)))
+        elif not vel:
             check(self.lib.irm_optimize_batch_dev(self._h, ctypes.byref(batch_dev), ctypes.c_void_p(stream)))
         else:
             check(self.lib.irm_optimize_batch_moving_dev(self._h, ctypes.byref(batch_dev), _dev(vel),

@@ -393,22 +393,32 @@ int fail_moving_lds(const char* fn, const irm_ctx* c, int O, int stride) {
                 "table (positions and velocities: twice the obstacle words)", fn, c->N, O, stride ? "per-problem" : "shared");
 }
 
-// Run one forward-family kernel on B host trajectories.  vel (nullable): the obstacles' velocities (O×2).
+// a host table of end-effector targets (B×2): every entry finite
+int check_goal_xy(const char* fn, const float* gxy, size_t B) {
+    for (size_t i = 0; i < 2 * B; ++i)
+        if (!std::isfinite(gxy[i])) return fail(IRM_EINVAL, "%s: goal_xy[%zu] is not finite", fn, i);
+    return 0;
+}
+
+// Run one forward-family kernel on B host trajectories.  vel (nullable): the obstacles' velocities (O×2);
+// gxy (nullable): the end-effector targets (B×2) of an end-effector-goal call.
 int run_forward(irm_ctx* c, int mode, const float* alpha, const float* start, const float* goal, const float* obs,
                 int O, int B, float lsg, float ljl, float lmax, int which, float* out0, float* out1, uint8_t* ok,
-                const float* vel = nullptr) {
+                const float* vel = nullptr, const float* gxy = nullptr) {
     if (set_device(c)) return IRM_EDEVICE;
     if (B < 0 || !alpha) return fail(IRM_EINVAL, "bad batch arguments");
     if (check_obs(O)) return IRM_EINVAL;
     if (!obs || O == 0) vel = nullptr;  // no obstacle, nothing moves
     if (vel && check_vel("irm_eval_cost(_grad)_moving", vel, (size_t)O * 2)) return IRM_EINVAL;
+    if (gxy && check_goal_xy("irm_eval_cost(_grad)_task / irm_constraints_task", gxy, (size_t)B)) return IRM_EINVAL;
     if (B == 0) return IRM_OK;
     const int N = c->N, D = c->D;
     const size_t nd = (size_t)B * N * D;
     Stage st{c};
     const size_t o_alpha = st.take(nd * 4), o_s = st.take((size_t)B * D * 4), o_g = st.take((size_t)B * D * 4),
                  o_obs = st.take((size_t)std::max(O, 1) * 8), o_out0 = st.take(std::max(nd, (size_t)B * 11) * 4),
-                 o_out1 = st.take(nd * 4), o_ok = st.take((size_t)B), o_vel = st.take((size_t)std::max(O, 1) * 8);
+                 o_out1 = st.take(nd * 4), o_ok = st.take((size_t)B), o_vel = st.take((size_t)std::max(O, 1) * 8),
+                 o_gxy = st.take((size_t)B * 8);
     if (ensure_io(c, st.off)) return IRM_ENOMEM;
     char* d = st.base();
     hipStream_t s = c->stream;
@@ -426,6 +436,11 @@ int run_forward(irm_ctx* c, int mode, const float* alpha, const float* start, co
     if (vel) {
         kp.moving = 1;
         kp.obs_vel = (const float*)(d + o_vel);
+    }
+    if (gxy) {
+        HIP_TRY(hipMemcpyAsync(d + o_gxy, gxy, (size_t)B * 8, hipMemcpyHostToDevice, s));
+        kp.task = 1;
+        kp.goal_xy = (const float*)(d + o_gxy);
     }
     kp.alpha0 = (const float*)(d + o_alpha);
     kp.start = (const float*)(d + o_s);
@@ -492,6 +507,68 @@ int irm_constraints(irm_ctx* c, const float* alpha, const float* start, const fl
                     float* report_out) {
     if (!c || !ok_out || !start || !goal) return fail(IRM_EINVAL, "irm_constraints: null argument");
     return run_forward(c, 3, alpha, start, goal, nullptr, 0, B, 0.f, 0.f, 0.f, 0, report_out, nullptr, ok_out);
+}
+
+int irm_eval_cost_task(irm_ctx* c, const float* alpha, const float* start, const float* goal, const float* obstacles,
+                       int32_t O, int32_t B, float lsg, float ljl, float lmax, float* cost_out,
+                       const float* obstacle_velocity, const float* goal_xy) {
+    if (!c || !cost_out || !start || !goal) return fail(IRM_EINVAL, "irm_eval_cost_task: null argument");
+    return run_forward(c, 1, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, nullptr, nullptr,
+                       obstacle_velocity, goal_xy);
+}
+
+int irm_eval_cost_grad_task(irm_ctx* c, const float* alpha, const float* start, const float* goal,
+                            const float* obstacles, int32_t O, int32_t B, float lsg, float ljl, float lmax,
+                            float* grad_out, float* cost_out, const float* obstacle_velocity, const float* goal_xy) {
+    if (!c || !grad_out || !start || !goal) return fail(IRM_EINVAL, "irm_eval_cost_grad_task: null argument");
+    return run_forward(c, 2, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, grad_out, nullptr,
+                       obstacle_velocity, goal_xy);
+}
+
+int irm_constraints_task(irm_ctx* c, const float* alpha, const float* start, const float* goal, int32_t B,
+                         uint8_t* ok_out, float* report_out, const float* goal_xy) {
+    if (!c || !ok_out || !start || !goal) return fail(IRM_EINVAL, "irm_constraints_task: null argument");
+    return run_forward(c, 3, alpha, start, goal, nullptr, 0, B, 0.f, 0.f, 0.f, 0, report_out, nullptr, ok_out, nullptr,
+                       goal_xy);
+}
+
+int irm_ik_seed_dev(irm_ctx* c, const float* start_dev, const float* goal_xy_dev, int32_t B, float* q_dev,
+                    float* residual_dev, void* stream) {
+    if (!c || !start_dev || !goal_xy_dev || !q_dev) return fail(IRM_EINVAL, "irm_ik_seed_dev: null argument");
+    if (B < 0) return fail(IRM_EINVAL, "irm_ik_seed_dev: negative batch");
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    KParams kp = c->kp;
+    kp.B = B;
+    // the joint range the seed stays in: the safety fraction of the limits (the optimiser's penalty thresholds)
+    const float lo = (float)((double)c->p.joint_safety_limit * (double)c->p.min_joint_position);
+    const float hi = (float)((double)c->p.joint_safety_limit * (double)c->p.max_joint_position);
+    HIP_TRY(irm::launch_ik_seed(kp, start_dev, goal_xy_dev, lo, hi, q_dev, residual_dev, (hipStream_t)stream));
+    return IRM_OK;
+}
+
+int irm_ik_seed(irm_ctx* c, const float* start, const float* goal_xy, int32_t B, float* q_out, float* residual_out) {
+    if (!c || !start || !goal_xy || !q_out) return fail(IRM_EINVAL, "irm_ik_seed: null argument");
+    if (B < 0) return fail(IRM_EINVAL, "irm_ik_seed: negative batch");
+    if (check_goal_xy("irm_ik_seed", goal_xy, (size_t)B)) return IRM_EINVAL;
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    const int D = c->D;
+    Stage st{c};
+    const size_t o_s = st.take((size_t)B * D * 4), o_p = st.take((size_t)B * 8), o_q = st.take((size_t)B * D * 4),
+                 o_r = st.take((size_t)B * 4);
+    if (ensure_io(c, st.off)) return IRM_ENOMEM;
+    char* d = st.base();
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d + o_s, start, (size_t)B * D * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_p, goal_xy, (size_t)B * 8, hipMemcpyHostToDevice, s));
+    const int rc = irm_ik_seed_dev(c, (const float*)(d + o_s), (const float*)(d + o_p), B, (float*)(d + o_q),
+                                   (float*)(d + o_r), s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(q_out, d + o_q, (size_t)B * D * 4, hipMemcpyDeviceToHost, s));
+    if (residual_out) HIP_TRY(hipMemcpyAsync(residual_out, d + o_r, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return IRM_OK;
 }
 
 int irm_fk(irm_ctx* c, const float* traj, int32_t B, float* pos_out, float* jac_out) {
@@ -586,8 +663,9 @@ int irm_init_alpha(irm_ctx* c, const float* start, const float* goal, int32_t B,
 
 namespace {
 
-// irm_optimize_batch_dev / irm_optimize_batch_moving_dev (vel: device pointer, NULL for the static launch)
-int optimize_dev(irm_ctx* c, const irm_batch_dev* a, const float* vel, void* stream) {
+// irm_optimize_batch_dev / irm_optimize_batch_moving_dev / irm_optimize_batch_task_dev (vel, gxy: device
+// pointers, NULL for static obstacles / the joint goal)
+int optimize_dev(irm_ctx* c, const irm_batch_dev* a, const float* vel, void* stream, const float* gxy = nullptr) {
     if (!c || !a) return fail(IRM_EINVAL, "irm_optimize_batch_dev: null argument");
     if (a->batch < 0 || !a->start || !a->goal) return fail(IRM_EINVAL, "bad batch arguments");
     if (check_obs(a->n_obstacles) || check_stride(a->n_obstacles, a->obstacle_stride)) return IRM_EINVAL;
@@ -611,6 +689,10 @@ int optimize_dev(irm_ctx* c, const irm_batch_dev* a, const float* vel, void* str
     if (vel && a->n_obstacles > 0) {
         kp.moving = 1;
         kp.obs_vel = vel;
+    }
+    if (gxy) {
+        kp.task = 1;
+        kp.goal_xy = gxy;
     }
     if (choose_shape(c, a->batch, true, kp, nullptr) <= 0)
         return kp.moving ? fail_moving_lds("irm_optimize_batch_moving", c, a->n_obstacles, a->obstacle_stride)
@@ -636,7 +718,7 @@ int optimize_dev(irm_ctx* c, const irm_batch_dev* a, const float* vel, void* str
 }
 
 int optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series, bool moving,
-                  irm_launch_plan* out) {
+                  irm_launch_plan* out, bool task = false) {
     if (!c || !out || batch <= 0) return fail(IRM_EINVAL, "irm_optimize_plan: bad argument");
     if (check_obs(n_obstacles)) return IRM_EINVAL;
     memset(out, 0, sizeof(*out));
@@ -647,6 +729,7 @@ int optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t 
     // for the series (irm_optimize_batch with series_out) — as in irm_optimize_batch(_dev)
     kp.record_series = (c->kp.record_series || record_series) ? 1 : 0;
     kp.moving = (moving && n_obstacles > 0) ? 1 : 0;
+    kp.task = task ? 1 : 0;
     if (choose_shape(c, batch, true, kp, nullptr) <= 0)
         return kp.moving ? fail_moving_lds("irm_optimize_plan_moving", c, n_obstacles, 0)
                          : fail(IRM_EINVAL, "no workgroup shape fits LDS");
@@ -687,6 +770,16 @@ int irm_optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int3
 int irm_optimize_plan_moving(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series,
                              irm_launch_plan* out) {
     return optimize_plan(c, batch, n_obstacles, record_series, true, out);
+}
+
+int irm_optimize_batch_task_dev(irm_ctx* c, const irm_batch_dev* a, const float* obstacle_velocity_dev,
+                                const float* goal_xy_dev, void* stream) {
+    return optimize_dev(c, a, obstacle_velocity_dev, stream, goal_xy_dev);
+}
+
+int irm_optimize_plan_task(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series,
+                           irm_launch_plan* out) {
+    return optimize_plan(c, batch, n_obstacles, record_series, false, out, true);
 }
 
 int irm_set_work_queue(irm_ctx* c, int32_t groups) {
@@ -1192,7 +1285,7 @@ namespace {
 
 int optimize_host(irm_ctx* c, const float* alpha0, const float* start, const float* goal, const float* obstacles,
                   int32_t O, int32_t obstacle_stride, int32_t B, float* alpha_out, float* traj_out,
-                  irm_stats* stats_out, float* series_out, const float* vel) {
+                  irm_stats* stats_out, float* series_out, const float* vel, const float* gxy = nullptr) {
     if (!c || !start || !goal) return fail(IRM_EINVAL, "irm_optimize_batch: null argument");
     if (check_obs(O) || check_stride(O, obstacle_stride)) return IRM_EINVAL;
     if (set_device(c)) return IRM_EDEVICE;
@@ -1203,14 +1296,16 @@ int optimize_host(irm_ctx* c, const float* alpha0, const float* start, const flo
     const size_t nser = series_out ? (size_t)B * c->max_series * N * D : 0;
     if (!obstacles || O == 0) vel = nullptr;
     if (vel && check_vel("irm_optimize_batch_moving", vel, nobs)) return IRM_EINVAL;
+    if (gxy && check_goal_xy("irm_optimize_batch_task", gxy, (size_t)B)) return IRM_EINVAL;
     Stage st{c};
     const size_t o_a0 = st.take(nd * 4), o_s = st.take((size_t)B * D * 4), o_g = st.take((size_t)B * D * 4),
                  o_o = st.take(std::max<size_t>(nobs, 1) * 4), o_ao = st.take(nd * 4), o_to = st.take(nd * 4),
                  o_st = st.take((size_t)B * sizeof(irm_stats)), o_se = st.take(std::max<size_t>(nser, 1) * 4),
-                 o_w = st.take(std::max<size_t>(nobs, 1) * 4);
+                 o_w = st.take(std::max<size_t>(nobs, 1) * 4), o_p = st.take((size_t)B * 8);
     if (ensure_io(c, st.off)) return IRM_ENOMEM;
     char* d = st.base();
     hipStream_t s = c->stream;
+    if (gxy) HIP_TRY(hipMemcpyAsync(d + o_p, gxy, (size_t)B * 8, hipMemcpyHostToDevice, s));
     if (alpha0) HIP_TRY(hipMemcpyAsync(d + o_a0, alpha0, nd * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_s, start, (size_t)B * D * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_g, goal, (size_t)B * D * 4, hipMemcpyHostToDevice, s));
@@ -1230,7 +1325,7 @@ int optimize_host(irm_ctx* c, const float* alpha0, const float* start, const flo
     a.series_out = series_out ? (float*)(d + o_se) : nullptr;
     KParams save = c->kp;
     if (series_out) c->kp.record_series = 1;
-    int rc = optimize_dev(c, &a, vel ? (const float*)(d + o_w) : nullptr, s);
+    int rc = optimize_dev(c, &a, vel ? (const float*)(d + o_w) : nullptr, s, gxy ? (const float*)(d + o_p) : nullptr);
     c->kp = save;
     if (rc) return rc;
     if (alpha_out) HIP_TRY(hipMemcpyAsync(alpha_out, d + o_ao, nd * 4, hipMemcpyDeviceToHost, s));
@@ -1258,6 +1353,14 @@ int irm_optimize_batch_moving(irm_ctx* c, const float* alpha0, const float* star
                               const float* obstacle_velocity) {
     return optimize_host(c, alpha0, start, goal, obstacles, O, obstacle_stride, B, alpha_out, traj_out, stats_out,
                          series_out, obstacle_velocity);
+}
+
+int irm_optimize_batch_task(irm_ctx* c, const float* alpha0, const float* start, const float* goal,
+                            const float* obstacles, int32_t O, int32_t obstacle_stride, int32_t B, float* alpha_out,
+                            float* traj_out, irm_stats* stats_out, float* series_out, const float* obstacle_velocity,
+                            const float* goal_xy) {
+    return optimize_host(c, alpha0, start, goal, obstacles, O, obstacle_stride, B, alpha_out, traj_out, stats_out,
+                         series_out, obstacle_velocity, goal_xy);
 }
 
 }  // extern "C"

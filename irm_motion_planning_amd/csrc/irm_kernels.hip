@@ -107,18 +107,102 @@ __global__ void k_init_alpha(KParams P, float* alpha_out) {
     alpha_out[e] = P.uvec[n] * sj + P.wvec[n] * gj;
 }
 
+// IK seed of an end-effector goal (irm_ik_seed, include/irm.h): damped least squares from `start`, one lane
+// per problem, fp32.  kIkIters iterations of
+//   e = f(q) − p,  dq = −J_eeᵀ·(J_ee·J_eeᵀ + μ²I)⁻¹·e  (μ = kIkMu, the 2×2 system in closed form),
+//   dq scaled to max|dq| ≤ kIkStep,  q ← clamp(q + dq, lo, hi)
+// then the residual ‖f(q) − p‖ of the returned q.  FK and Jacobian as k_fk forms them.
+constexpr int kIkIters = 32;
+constexpr float kIkMu = 0.1f, kIkStep = 0.5f;
+template <int D>
+__global__ void k_ik_seed(KParams P, const float* __restrict__ start, const float* __restrict__ goal_xy, float lo,
+                          float hi, float* __restrict__ q_out, float* __restrict__ res_out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= P.B) return;
+    const float px = goal_xy[(size_t)b * 2], py = goal_xy[(size_t)b * 2 + 1];
+    float q[D], jx[D], jy[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) q[d] = start[(size_t)b * D + d];
+    float ex = 0.f, ey = 0.f;
+    // e = f(q) − p and, with `jac`, J_ee at q
+    auto fk = [&](bool jac) {
+        float cum = 0.f, fx = 0.f, fy = 0.f, Sx = 0.f, Sy = 0.f, xs[D], ys[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            cum += q[d];
+            float sn, cs;
+            sincos_fast(cum, sn, cs);
+            fx = fmaf(P.link[d], cs, fx);
+            fy = fmaf(P.link[d], sn, fy);
+            xs[d] = -(P.link[d] * sn);
+            ys[d] = P.link[d] * cs;
+            Sx += xs[d];
+            Sy += ys[d];
+        }
+        ex = fx - px;
+        ey = fy - py;
+        if (!jac) return;
+        float Cx = 0.f, Cy = 0.f;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            Cx += xs[d];
+            Cy += ys[d];
+            jx[d] = (xs[d] + Sx) - Cx;
+            jy[d] = (ys[d] + Sy) - Cy;
+        }
+    };
+    for (int it = 0; it < kIkIters; ++it) {
+        fk(true);
+        float a11 = kIkMu * kIkMu, a12 = 0.f, a22 = kIkMu * kIkMu;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            a11 = fmaf(jx[d], jx[d], a11);
+            a12 = fmaf(jx[d], jy[d], a12);
+            a22 = fmaf(jy[d], jy[d], a22);
+        }
+        // y = A⁻¹·e; det ≥ μ⁴ > 0 (A = J·Jᵀ + μ²I is positive definite)
+        const float det = fmaf(a11, a22, -(a12 * a12));
+        const float y0 = fmaf(a22, ex, -(a12 * ey)) / det;
+        const float y1 = fmaf(a11, ey, -(a12 * ex)) / det;
+        float dq[D], m = 0.f;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            dq[d] = -fmaf(jx[d], y0, jy[d] * y1);
+            m = fmaxf(m, fabsf(dq[d]));
+        }
+        const float sc = m > kIkStep ? kIkStep / m : 1.f;
+#pragma unroll
+        for (int d = 0; d < D; ++d) q[d] = fminf(fmaxf(fmaf(sc, dq[d], q[d]), lo), hi);
+    }
+    fk(false);
+#pragma unroll
+    for (int d = 0; d < D; ++d) q_out[(size_t)b * D + d] = q[d];
+    if (res_out) res_out[b] = sqrtf(fmaf(ey, ey, ex * ex));
+}
+
+hipError_t launch_ik_seed(const KParams& p, const float* start, const float* goal_xy, float lo, float hi, float* q_out,
+                          float* res_out, hipStream_t s) {
+    if (p.B <= 0) return hipSuccess;
+    return dispatch_d(p.D, [&](auto dc) {
+        constexpr int DD = decltype(dc)::value;
+        hipLaunchKernelGGL(k_ik_seed<DD>, dim3((p.B + 63) / 64), dim3(64), 0, s, p, start, goal_xy, lo, hi, q_out, res_out);
+        return hipGetLastError();
+    });
+}
+
 hipError_t launch_optimize(const KParams& p, hipStream_t s, LaunchDesc* desc) {
     // the dense operator (--operator-rank -1) of BASELINE configs[4]'s shape (7-DoF, N = 256): k_lean's GD
     // single loop over DenseShape (the other flows, workgroup sizes: the general kernel below)
     // (a moving launch runs k_optimize<DynShape<D>>, as a whole-robot launch does: the shape-specialised
-    // kernels have no moving variant, and k_optimize has no work queue)
-    if (p.v_ident && p.D == 7 && p.N == 256 && p.RP == p.NK && !p.whole_robot && !p.moving && p.lean_ok) {
+    // kernels have no moving variant, and k_optimize has no work queue; an end-effector-goal launch, p.task,
+    // likewise)
+    if (p.v_ident && p.D == 7 && p.N == 256 && p.RP == p.NK && !p.whole_robot && !p.moving && !p.task && p.lean_ok) {
         bool served = false;
         const hipError_t e = launch_dense_shape<DenseShape<7, 256>>(p, s, desc, &served);
         if (served) return e;
     }
     // shape-specialised kernels for the common configurations (auto rank R = 32)
-    if (p.RP == 32 && p.nsplit == stage1_splits(p.NK) && !p.whole_robot && !p.moving) {
+    if (p.RP == 32 && p.nsplit == stage1_splits(p.NK) && !p.whole_robot && !p.moving && !p.task) {
 #define IRM_TRY_FIX(D_, N_) \
         if (p.D == D_ && p.N == N_) return launch_optimize_shape<FixShape<D_, N_, 32>>(p, s, desc);
         IRM_FIX_SHAPES(IRM_TRY_FIX)

@@ -18,6 +18,10 @@ hipError_t launch_forward(const KParams& p, int mode, hipStream_t s);  // mode: 
 hipError_t launch_fk(const KParams& p, const float* traj, float* pos, float* jac, hipStream_t s);
 hipError_t launch_fk_joints(const KParams& p, const float* traj, float* pos, hipStream_t s);
 hipError_t launch_cost_vg(const KParams& p, const float* f, float* cv, float* cg, hipStream_t s);
+// IK seed of an end-effector goal (irm_ik_seed): p.B problems, start B×D, goal_xy B×2, joint range [lo, hi];
+// q_out B×D, res_out B (nullable), device pointers
+hipError_t launch_ik_seed(const KParams& p, const float* start, const float* goal_xy, float lo, float hi, float* q_out,
+                          float* res_out, hipStream_t s);
 // irm_dense.hip — evaluation at arbitrary times.  mT / kqT / dkqT: query matrices on the device, transposed
 // ([N][M]); α from p.alpha0 (B×N×D), obstacles from p.obstacles / p.O / p.obs_stride.
 hipError_t launch_eval_any(const KParams& p, const float* mT, int M, float* out, hipStream_t s);

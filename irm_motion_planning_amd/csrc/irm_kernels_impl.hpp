@@ -227,6 +227,26 @@ struct WP {
     float zm[D], zvm[D];     // LEAN: masked (q − μ)/σ_q and v/v_max (0 where the limit mask is off)
 };
 
+// End-effector goal (P.task, include/irm.h): what the end row's terms need of a waypoint's evaluation — the
+// end-effector position f the evaluation itself formed and the end effector's Jacobian J_ee (with WHOLE,
+// WP::jx holds the whole-robot gradient instead).
+template <int D>
+struct EE {
+    float fx, fy;
+    float jx[D], jy[D];
+};
+
+// The end row's terms of an end-effector goal from its evaluation, in the fp32 order include/irm.h defines:
+//   e = f − p,  r² = fmaf(e_y, e_y, e_x·e_x),  ge[d] = fmaf(J_y[d], e_y, J_x[d]·e_x)  (= J_eeᵀ·e)
+// r² takes the place of ‖T[N−1] − g‖² (loss, constraint) and ge that of T[N−1] − g (gradient input a).
+template <int D>
+__device__ __forceinline__ void task_end_row(const EE<D>& ee, float px, float py, float (&ge)[D], float& r2) {
+    const float ex = ee.fx - px, ey = ee.fy - py;
+    r2 = fmaf(ey, ey, ex * ex);
+#pragma unroll
+    for (int d = 0; d < D; ++d) ge[d] = fmaf(ee.jy[d], ey, ee.jx[d] * ex);
+}
+
 // robot.py:29-36 (fk), 75-87 (jacobian); environment.py:46-58
 // (compute_cost_vg); trajectory.py:215-227, 245-255 (penalty elements).
 // WHOLE: the potential is summed over every joint position p_j = fk_joint_j
@@ -264,12 +284,14 @@ __device__ __forceinline__ void lean_pen(const KParams& P, const float (&q)[D], 
 // obstacle pair, from the velocity table `vel` (LDS, stage_obstacles' layout; sentinel velocity 0, so the
 // padding stays at 1e20 and adds exactly 0).  From there on the arithmetic is the static one's; a zero
 // velocity gives the static result to the bit (fmaf(tau, 0, p) = p).
-template <int D, bool WHOLE = false, bool POT = true, bool LEAN = false, bool MOVING = false>
+// TASK: *ee receives f and J_ee as formed here (no second FK); nothing else changes.
+template <int D, bool WHOLE = false, bool POT = true, bool LEAN = false, bool MOVING = false, bool TASK = false>
 __device__ __forceinline__ void eval_waypoint(const KParams& P, const float (&q)[D], const float (&v)[D],
                                               const float* __restrict__ ob, WP<D>& w,
                                               const f32x4* oreg = nullptr,  // oreg: the 12-obstacle
                                                                             // table held in VGPRs
-                                              const float* __restrict__ vel = nullptr, float tau = 0.f) {
+                                              const float* __restrict__ vel = nullptr, float tau = 0.f,
+                                              EE<D>* ee = nullptr) {
     float fx = 0.f, fy = 0.f, Sx = 0.f, Sy = 0.f;
     float xs[D], ys[D], px[D], py[D], cum[D], snv[D], csv[D];
     bool big = false;
@@ -380,6 +402,10 @@ __device__ __forceinline__ void eval_waypoint(const KParams& P, const float (&q)
         ax = -3.2f * (ax2.x + ax2.y);
         ay = -3.2f * (ay2.x + ay2.y);
     };
+    if constexpr (TASK) {
+        ee->fx = fx;
+        ee->fy = fy;
+    }
     if constexpr (!WHOLE) {
         float Cx = 0.f, Cy = 0.f;
 #pragma unroll
@@ -388,6 +414,10 @@ __device__ __forceinline__ void eval_waypoint(const KParams& P, const float (&q)
             Cy = d ? Cy + ys[d] : ys[d];
             w.jx[d] = (xs[d] + Sx) - Cx;
             w.jy[d] = (ys[d] + Sy) - Cy;
+            if constexpr (TASK) {
+                ee->jx[d] = w.jx[d];
+                ee->jy[d] = w.jy[d];
+            }
         }
         if constexpr (POT) {
             potential(fx, fy, w.cv, w.gx, w.gy);
@@ -396,6 +426,16 @@ __device__ __forceinline__ void eval_waypoint(const KParams& P, const float (&q)
             w.fy = fy;
         }
     } else {
+        if constexpr (TASK) {  // J_ee in the order of the end-effector variant above
+            float Cx = 0.f, Cy = 0.f;
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                Cx = d ? Cx + xs[d] : xs[d];
+                Cy = d ? Cy + ys[d] : ys[d];
+                ee->jx[d] = (xs[d] + Sx) - Cx;
+                ee->jy[d] = (ys[d] + Sy) - Cy;
+            }
+        }
         float cvt = 0.f, gxj[D], gyj[D];
 #pragma unroll
         for (int j = 0; j < D; ++j) {
@@ -482,26 +522,30 @@ __device__ __forceinline__ void potential_pair(const KParams& P, const float* __
 
 // eval_waypoint with the cost variant chosen at run time (host-API kernels, DynShape optimiser).
 // vel / tau: the moving variant (P.moving; vel the LDS velocity table behind ob's, tau the lane's time)
-template <int D>
+// TASK: *ee receives f and J_ee (eval_waypoint; the caller decides at run time whether it uses them)
+template <int D, bool TASK = false>
 __device__ __forceinline__ void eval_waypoint_rt(const KParams& P, const float (&q)[D], const float (&v)[D],
                                                  const float* __restrict__ ob, WP<D>& w,
-                                                 const float* __restrict__ vel = nullptr, float tau = 0.f) {
+                                                 const float* __restrict__ vel = nullptr, float tau = 0.f,
+                                                 EE<D>* ee = nullptr) {
     if (P.moving) {
-        if (P.whole_robot) eval_waypoint<D, true, true, false, true>(P, q, v, ob, w, nullptr, vel, tau);
-        else eval_waypoint<D, false, true, false, true>(P, q, v, ob, w, nullptr, vel, tau);
+        if (P.whole_robot) eval_waypoint<D, true, true, false, true, TASK>(P, q, v, ob, w, nullptr, vel, tau, ee);
+        else eval_waypoint<D, false, true, false, true, TASK>(P, q, v, ob, w, nullptr, vel, tau, ee);
         return;
     }
-    if (P.whole_robot) eval_waypoint<D, true>(P, q, v, ob, w);
-    else eval_waypoint<D, false>(P, q, v, ob, w);
+    if (P.whole_robot) eval_waypoint<D, true, true, false, false, TASK>(P, q, v, ob, w, nullptr, nullptr, 0.f, ee);
+    else eval_waypoint<D, false, true, false, false, TASK>(P, q, v, ob, w, nullptr, nullptr, 0.f, ee);
 }
 
 // Gradient inputs a (→ Kᵀ) and b (→ dKᵀ) of one waypoint, trajectory.py:91-126
 // (obstacle), 191-212 (start/goal), 231-242 / 259-268 (joint limits).
+// task_row: this lane is row N−1 of an end-effector-goal call and g holds ge = J_eeᵀ·(f − p)
+// (task_end_row), which takes the place of q − g.
 template <int D>
 __device__ __forceinline__ void grad_waypoint(const KParams& P, const WP<D>& w, const float (&q)[D],
                                               const float (&v)[D], int n, int idx, float lsg, float ljl,
                                               const float (&s)[D], const float (&g)[D], float (&a)[D],
-                                              float (&b)[D]) {
+                                              float (&b)[D], bool task_row = false) {
     const int N = P.N;
     const float wt = (n == idx ? P.lam_max : 0.f) + P.one_m_lmax * P.invN;
     const float wx = wt * w.gx, wy = wt * w.gy;
@@ -513,7 +557,7 @@ __device__ __forceinline__ void grad_waypoint(const KParams& P, const WP<D>& w, 
             sgv = v[d];
         }
         if (n == N - 1) {
-            sgp = q[d] - g[d];
+            sgp = task_row ? g[d] : q[d] - g[d];
             sgv = v[d];
         }
         float jpg = 0.f, jvg = 0.f;
@@ -545,11 +589,13 @@ __device__ __forceinline__ LeanW lean_weights(const KParams& P, float ljl) {
 // Gradient inputs a, b of one waypoint from a LEAN evaluation (grad_waypoint's terms, the penalty
 // masks and normalised deviations reused from the evaluation).  lsg_ep = λsg on rows 0 and N−1, else
 // 0 (per lane); tg the row's start / goal.
-template <int D>
+// TASK (k_optimize<DynShape<D>>): on the lane with task_row — row N−1 of an end-effector-goal launch — tg
+// holds ge = J_eeᵀ·(f − p) (task_end_row), which takes the place of q − tg.
+template <int D, bool TASK = false>
 __device__ __forceinline__ void grad_waypoint_lean(const KParams& P, const WP<D>& w, const float (&q)[D],
                                                    const float (&v)[D], bool isidx, float lsg_ep,
                                                    const LeanW& c, const float (&tg)[D], float (&a)[D],
-                                                   float (&b)[D]) {
+                                                   float (&b)[D], bool task_row = false) {
     const float wt = (isidx ? P.lam_max : 0.f) + c.c_mean;
     const float wx = wt * w.gx, wy = wt * w.gy;
     float zm[D], zvm[D];
@@ -564,7 +610,9 @@ __device__ __forceinline__ void grad_waypoint_lean(const KParams& P, const WP<D>
     }
 #pragma unroll
     for (int d = 0; d < D; ++d) {
-        a[d] = fmaf(c.k_pos, zm[d], fmaf(lsg_ep, q[d] - tg[d], fmaf(wx, w.jx[d], wy * w.jy[d])));
+        float sgp = q[d] - tg[d];
+        if constexpr (TASK) sgp = task_row ? tg[d] : sgp;
+        a[d] = fmaf(c.k_pos, zm[d], fmaf(lsg_ep, sgp, fmaf(wx, w.jx[d], wy * w.jy[d])));
         b[d] = fmaf(lsg_ep, v[d], c.k_vel * zvm[d]);
     }
 }
@@ -581,7 +629,9 @@ struct EvalOut {
 template <int D>
 __device__ __forceinline__ void eval_partials(const KParams& P, bool live, const WP<D>& w, int n, int wave,
                                               const float (&q)[D], const float (&v)[D], const float (&s)[D],
-                                              const float (&g)[D], float* red, float* sg, int t) {
+                                              const float (&g)[D], float* red, float* sg, int t,
+                                              bool task_row = false, float r2 = 0.f) {  // task_row: row N−1 of
+                                              // an end-effector-goal call stores r² = ‖f − p‖² (task_end_row)
     float cmax = live ? w.cv : -INFINITY;
     int cidx = live ? n : 0x7fffffff;
     wred_argmax(cmax, cidx);
@@ -610,6 +660,7 @@ __device__ __forceinline__ void eval_partials(const KParams& P, bool live, const
             a += e * e;
             bb += v[d] * v[d];
         }
+        if (task_row) a = r2;
         sg[t * 4 + (n == 0 ? 0 : 2)] = a;
         sg[t * 4 + (n == 0 ? 1 : 3)] = bb;
     }
@@ -1302,6 +1353,10 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
             tau = valid ? P.tsup[n] : 0.f;
         }
     }
+    // end-effector goal (DynShape launches only): the lane of row N−1 (it reads its problem's target in every
+    // evaluation — one lane, an L2 hit — so that nothing more stays in registers across the rounds)
+    bool task_row = false;
+    if constexpr (S::kVariants) task_row = P.task && valid && n == N - 1;
 
     // stage 1 over the units of this wave: Ypart[s] = Fᵀ·[a'; b'] (velocity half if `full`)
     auto stage1 = [&](bool full) {
@@ -1753,13 +1808,18 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
         const bool ev = (phase != PH_DONE);  // wave-uniform
         WP<D> w;
         if (ev) {
+            float task_r2 = 0.f;
             if (valid) {
                 if constexpr (S::kVariants) {
+                    EE<D> ee;
                     if (P.moving) {  // this waypoint's obstacle table is the one at its support time
-                        if (P.whole_robot) eval_waypoint<D, true, true, true, true>(P, q2, v2, obs, w, nullptr, obsv, tau);
-                        else eval_waypoint<D, false, true, true, true>(P, q2, v2, obs, w, nullptr, obsv, tau);
-                    } else if (P.whole_robot) eval_waypoint<D, true, true, true>(P, q2, v2, obs, w);
-                    else eval_waypoint<D, false, true, true>(P, q2, v2, obs, w);
+                        if (P.whole_robot) eval_waypoint<D, true, true, true, true, true>(P, q2, v2, obs, w, nullptr, obsv, tau, &ee);
+                        else eval_waypoint<D, false, true, true, true, true>(P, q2, v2, obs, w, nullptr, obsv, tau, &ee);
+                    } else if (P.whole_robot) eval_waypoint<D, true, true, true, false, true>(P, q2, v2, obs, w, nullptr, nullptr, 0.f, &ee);
+                    else eval_waypoint<D, false, true, true, false, true>(P, q2, v2, obs, w, nullptr, nullptr, 0.f, &ee);
+                    // end-effector goal: the end row's ge = J_eeᵀ·(f − p) replaces this lane's copy of the
+                    // joint goal (not read again in such a launch) and r² the squared joint distance below
+                    if (task_row) task_end_row<D>(ee, P.goal_xy[b * 2], P.goal_xy[b * 2 + 1], g, task_r2);
                 } else {
                     eval_waypoint<D, false, true, true>(P, q2, v2, obs, w);
                 }
@@ -1776,6 +1836,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
                     a = fmaf(e, e, a);
                     bb = fmaf(v2[d], v2[d], bb);
                 }
+                if constexpr (S::kVariants) a = task_row ? task_r2 : a;
                 sg[t * 4 + (n == 0 ? 0 : 2)] = a;
                 sg[t * 4 + (n == 0 ? 1 : 3)] = bb;
             }
@@ -1913,7 +1974,8 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
                 const bool endrow = (n == 0 || n == N - 1);
 #pragma unroll
                 for (int k = 0; k < D; ++k) tg[k] = (n == N - 1) ? g[k] : s[k];
-                grad_waypoint_lean<D>(P, w, q2, v2, n == cidx, endrow ? lsg_e : 0.f, lean_weights(P, ljl_e), tg, a, bb);
+                grad_waypoint_lean<D, S::kVariants>(P, w, q2, v2, n == cidx, endrow ? lsg_e : 0.f, lean_weights(P, ljl_e),
+                                                    tg, a, bb, task_row);
 #pragma unroll
                 for (int k = 0; k < D; ++k) {
                     float ma = 0.f, mb = 0.f;
@@ -4449,10 +4511,15 @@ __global__ __launch_bounds__(MAXT) void k_forward(KParams P, int mode) {
         return;
     }
     WP<D> w;
+    const bool task_row = P.task && valid && n == N - 1;
+    float task_r2 = 0.f;
     if (tvalid) {
         // (obstacles: shared only here, obs_stride 0 — the velocity table follows the one position table)
-        if (valid) eval_waypoint_rt<D>(P, q, v, obsL, w, obsL + obs_vel_offset(P), P.moving ? P.tsup[n] : 0.f);
-        eval_partials<D>(P, valid, w, n, wave, q, v, s, g, red, sg, t);
+        EE<D> ee;
+        if (valid) eval_waypoint_rt<D, true>(P, q, v, obsL, w, obsL + obs_vel_offset(P), P.moving ? P.tsup[n] : 0.f, &ee);
+        // end-effector goal: ge = J_eeᵀ·(f − p) replaces this lane's copy of the joint goal
+        if (task_row) task_end_row<D>(ee, P.goal_xy[b * 2], P.goal_xy[b * 2 + 1], g, task_r2);
+        eval_partials<D>(P, valid, w, n, wave, q, v, s, g, red, sg, t, task_row, task_r2);
     }
     __syncthreads();
     EvalOut E{};
@@ -4477,7 +4544,7 @@ __global__ __launch_bounds__(MAXT) void k_forward(KParams P, int mode) {
     if (mode != 2) return;
     if (valid) {
         float a[D], bb[D];
-        grad_waypoint<D>(P, w, q, v, n, E.idx, P.lam_sg, P.lam_jl, s, g, a, bb);
+        grad_waypoint<D>(P, w, q, v, n, E.idx, P.lam_sg, P.lam_jl, s, g, a, bb, task_row);
 #pragma unroll
         for (int k = 0; k < D; ++k) {
             XG[n * kLd + t * D + k] = a[k];

@@ -119,6 +119,11 @@ struct KParams {
     const float* obs_vel;
     const float* tsup;
     int32_t moving;
+    // end-effector goal (irm_*_task): row N−1 is held to the Cartesian target goal_xy[b] (B×2) instead of
+    // the joint configuration goal[b] — loss, gradient input and constraint, include/irm.h.  Appended like
+    // the moving block.  task: the launch reads goal_xy (k_forward, k_optimize<DynShape<D>>)
+    int32_t task;
+    const float* goal_xy;
 };
 
 constexpr int kTraceW = 10;  // outer, inner, trial, lr, new_loss, required_loss, accepted, loss, ‖g‖, alpha_norm

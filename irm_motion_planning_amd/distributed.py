@@ -38,14 +38,16 @@ def _dist():
     return dist
 
 
-def broadcast_environment(obstacles, start=None, goal=None, device="cpu", src=0):
+def broadcast_environment(obstacles, start=None, goal=None, device="cpu", src=0, goal_xy=None):
     """Rank src's obstacles (O×2 or B×O×2) and optional start/goal (B×D) on every rank.
 
-    Shapes must agree across ranks (the batch size is a CLI argument); values come from src."""
+    Shapes must agree across ranks (the batch size is a CLI argument); values come from src.
+    goal_xy (B×2, --goal-xy): the end-effector targets travel with the goals — a fourth array in the result,
+    which every rank slices with shard() like start and goal."""
     import torch
     dist = _dist()
     out = []
-    for a in (obstacles, start, goal):
+    for a in (obstacles, start, goal) + (() if goal_xy is None else (goal_xy,)):
         if a is None:
             out.append(None)
             continue

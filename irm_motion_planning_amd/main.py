@@ -9,8 +9,10 @@ files trajectory_result.txt / trajectory_series.txt (np.savetxt defaults).
 Additive flags (no reference counterpart): --batch-size, --seed,
 --operator-rank, --device, --whole-robot-cost, --work-queue, --dense-check
 (which adds one stdout line and trajectory_result_dense.txt),
---coarse-n-timesteps (coarse-to-fine: two stdout lines per optimize()) and
---obstacle-velocity (obstacles that drift at a constant velocity over the plan).
+--coarse-n-timesteps (coarse-to-fine: two stdout lines per optimize()),
+--obstacle-velocity (obstacles that drift at a constant velocity over the plan) and
+--goal-xy (an end-effector target instead of a goal configuration; the goal number of the
+"start goal position" line is then the Cartesian distance).
 """
 import argparse
 import os
@@ -138,6 +140,12 @@ def build_parser():
                         help="Every obstacle of every problem drifts by (VX, VY) over the plan (t in [0, 1]): the "
                              "optimiser and --dense-check see obstacle o at p + t*(VX, VY) at plan time t "
                              "(default: absent = static obstacles)")
+    parser.add_argument('--goal-xy', type=float, nargs=2, default=None, metavar=('X', 'Y'),
+                        help="Plan to an end-effector target instead of a goal configuration: the end effector "
+                             "of the last waypoint is held to (X, Y); the goal configuration (the initial line) is "
+                             "the IK seed from the start.  With --batch-size, problem 0 takes (X, Y) and every "
+                             "seeded problem the end-effector position of its seeded goal configuration "
+                             "(default: absent = joint goal)")
     return parser
 
 
@@ -209,14 +217,28 @@ def run_batch(optimizer, args):
     world, rank, _ = distributed.world_info()
     B = args.batch_size
     start, goal = batch_io.batch_problems(B, tr.robot.N_joints, args.seed)
+    goal_xy = None
+    if optimizer.goal_xy is not None:
+        # --goal-xy: every seeded problem is planned to the end-effector position of its seeded goal
+        # configuration, problem 0 (the environment's) to the flag's target from its IK seed
+        links = np.asarray(tr.robot.link_length, np.float64)[:tr.robot.N_joints]
+        angles = np.cumsum(goal.astype(np.float64), axis=1)
+        goal_xy = np.stack([(links * np.cos(angles)).sum(1), (links * np.sin(angles)).sum(1)], axis=1).astype(np.float32)
+        goal_xy[0] = optimizer.goal_xy
+        goal = np.array(goal, np.float32)
+        goal[0] = env.goal_config
     lo, hi = 0, B
     dev = "cpu"
     if world > 1:
         import torch
         dev = torch.device("cuda", args.device) if torch.distributed.get_backend() == "nccl" else "cpu"
-        obs, start, goal = distributed.broadcast_environment(env.obstacles, start, goal, dev)
+        if goal_xy is None:
+            obs, start, goal = distributed.broadcast_environment(env.obstacles, start, goal, dev)
+        else:  # the targets are sharded with the goals
+            obs, start, goal, goal_xy = distributed.broadcast_environment(env.obstacles, start, goal, dev, goal_xy=goal_xy)
         env.obstacles = obs
         lo, hi = distributed.shard(B, world, rank)
+    xy = None if goal_xy is None else goal_xy[lo:hi]
     wq = getattr(args, "work_queue", "off")
     if wq != "off":  # this process's launch (single GPU, or this rank's shard)
         ctx = optimizer.context
@@ -231,9 +253,11 @@ def run_batch(optimizer, args):
         st = time.time()
         for _ in range(args.n_times):
             if coarse is not None:  # this process's problems (single GPU, or this rank's shard)
-                res = optimizer.coarse_to_fine(coarse, start[lo:hi], goal[lo:hi], env.obstacles, series=args.extended_vis)
+                res = optimizer.coarse_to_fine(coarse, start[lo:hi], goal[lo:hi], env.obstacles, series=args.extended_vis,
+                                               goal_xy=xy)
             else:
-                res = optimizer.optimize_batch(start[lo:hi], goal[lo:hi], env.obstacles, series=args.extended_vis)
+                res = optimizer.optimize_batch(start[lo:hi], goal[lo:hi], env.obstacles, series=args.extended_vis,
+                                               goal_xy=xy)
         et = time.time()
         if world > 1:
             et = st + distributed.reduce_timing(et - st, 0, dev)[0]
@@ -259,12 +283,13 @@ def run_batch(optimizer, args):
         series = full.get("series")
     avg = tr.compute_trajectory_cost(alpha, env.obstacles, start, goal, 0, 0, 0)
     mx = tr.compute_trajectory_cost(alpha, env.obstacles, start, goal, 0, 0, 1)
-    ok, _ = optimizer.context.constraints(alpha, start, goal)
+    ok, _ = optimizer.context.constraints(alpha, start, goal, goal_xy=goal_xy)
     print("batch of", len(alpha), "problems" + (f" on {world} GPUs" if world > 1 else "") +
           ": constraint fulfiled", int(np.sum(ok)), "of", len(alpha),
           "; avg cost mean", float(np.mean(avg)), ", max cost mean", float(np.mean(mx)),
           "; inner iterations", int(np.sum(stats["inner_iterations"])))
-    ok0 = tr.constraintsFulfilledVerbose(alpha[0], start[0], goal[0], verbose=True)
+    ok0 = tr.constraintsFulfilledVerbose(alpha[0], start[0], goal[0], verbose=True,
+                                         goal_xy=None if goal_xy is None else goal_xy[0])
     print("result cost: ( avg", avg[0], ", max", mx[0], "). constraint fulfiled", ok0)
     if getattr(args, "dense_check", 0) > 0:
         rep = dense_report(optimizer.context, alpha, env.obstacles, args.dense_check, optimizer.obstacle_velocity)
@@ -315,7 +340,8 @@ def main(argv=None):
     def coarse_to_fine():
         """optimizer.optimize() through the coarse stage: α, or (α, series) with --extended-vis."""
         env = optimizer.env
-        res = optimizer.coarse_to_fine(coarse, env.start_config, env.goal_config, series=args.extended_vis)
+        res = optimizer.coarse_to_fine(coarse, env.start_config, env.goal_config, series=args.extended_vis,
+                                       goal_xy=optimizer.goal_xy)
         if args.extended_vis:
             return res[0][0], [np.array(f) for f in res[3][0][: int(res[2]["series_len"][0])]]
         return res[0][0]
@@ -347,7 +373,8 @@ def main(argv=None):
     env, tr = optimizer.env, optimizer.trajectory
     avg_result_cost = tr.compute_trajectory_cost(result_alpha, env.obstacles, env.start_config, env.goal_config, 0, 0, 0)
     max_result_cost = tr.compute_trajectory_cost(result_alpha, env.obstacles, env.start_config, env.goal_config, 0, 0, 1)
-    ok = tr.constraintsFulfilledVerbose(result_alpha, env.start_config, env.goal_config, verbose=True)
+    ok = tr.constraintsFulfilledVerbose(result_alpha, env.start_config, env.goal_config, verbose=True,
+                                        goal_xy=optimizer.goal_xy)
     print("result cost: ( avg", avg_result_cost, ", max", max_result_cost, "). constraint fulfiled", ok)
 
     np_trajectory = np.array(tr.evaluate(result_alpha, tr.km, tr.jac))

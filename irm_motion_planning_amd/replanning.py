@@ -22,6 +22,11 @@ straight line of initTrajectory (optimizer_BLS.py:57-62).
   plan (waypoint n sees obstacle o at p + t[n]·w); the velocity table lives on the device next to the
   obstacle table, and advance(tau) moves both to the new plan's time origin (advance_obstacles).
 
+* plan(..., goal_xy=p) plans to end-effector targets (B×2 or 2) instead of goal configurations; the table
+  lives on the device between plans (plan() without goal_xy and without goal keeps it), and advance(tau)
+  carries it — the target is a point of the world, not of the plan's time.  Without a goal configuration the
+  first such plan seeds its straight line with the IK seed (irm_ik_seed_dev), on the device.
+
 The first call, or warm_start=False, is exactly Optimizer.optimize() for the batch.
 A warm-started call equals irm_optimize_batch with alpha0 = the previous α_out bit for
 bit (tests/test_gpu_parity.py::test_replanner_*).
@@ -67,6 +72,8 @@ class Replanner:
         self.velocity = torch.zeros_like(self.obstacles)  # the obstacles' velocities (plan(obstacle_velocity=…))
         self.moving = False       # did the latest plan have velocities?
         self._have_obs = False    # is there a stored obstacle table (plan(obstacles=None))?
+        self.goal_xy = torch.zeros((B, 2), **f32)  # end-effector targets (plan(goal_xy=…))
+        self.task = False         # does the latest plan hold the end effector to goal_xy?
         self._alpha = [torch.zeros((B, N, D), **f32), torch.zeros((B, N, D), **f32)]
         self.traj = torch.zeros((B, N, D), **f32)
         self.stats = torch.zeros((B, len(STATS_FIELDS)), dtype=torch.int32, device=self.device)
@@ -79,14 +86,18 @@ class Replanner:
         x = np.array(np.broadcast_to(np.asarray(x, np.float32), shape))  # writable copy
         dst.copy_(self.torch.from_numpy(x).reshape(dst.shape), non_blocking=False)
 
-    def plan(self, obstacles=None, start=None, goal=None, warm_start=True, stream=None, obstacle_velocity=None):
+    def plan(self, obstacles=None, start=None, goal=None, warm_start=True, stream=None, obstacle_velocity=None,
+             goal_xy=None):
         """Optimise the batch against `obstacles` (O×2, or B×O×2 per problem).
 
         start / goal (B×D or D) are kept from the previous call when None.  obstacles=None re-uses the
         stored table (as advance() left it; an IrmError on the first call) and, unless obstacle_velocity
         is given, the stored velocities; passing obstacles overrides the stored table, as fresh perception
         would, and then the obstacles are static unless obstacle_velocity (the obstacles' shape) says
-        otherwise.  Returns the per-problem statistics (dict of numpy arrays, irm_stats fields); the plan
+        otherwise.  goal_xy (B×2 or 2): plan to these end-effector targets; a later plan() with neither
+        goal nor goal_xy keeps them, one with a goal configuration alone goes back to the joint goal.  A
+        first plan with goal_xy and no goal seeds the goal configuration with the IK seed from `start`.
+        Returns the per-problem statistics (dict of numpy arrays, irm_stats fields); the plan
         stays on the device (alpha(), trajectory())."""
         torch = self.torch
         B, D, O = self.B, self.D, self.O
@@ -110,8 +121,23 @@ class Replanner:
             self._put(self.start, start, (B, D))
         if goal is not None:
             self._put(self.goal, goal, (B, D))
-        if self.calls == 0 and (start is None or goal is None):
-            raise IrmError("the first plan() needs start and goal")
+        gxy = None
+        if goal_xy is not None:
+            gxy = np.asarray(goal_xy, np.float32)
+            if gxy.shape not in ((B, 2), (2,)):
+                raise IrmError(f"goal_xy must have shape {(B, 2)} or (2,), got {gxy.shape}")
+            if not np.all(np.isfinite(gxy)):
+                raise IrmError("goal_xy must be finite")
+            self._put(self.goal_xy, gxy, (B, 2))
+            self.task = True
+        elif goal is not None:
+            self.task = False
+        if self.calls == 0 and (start is None or (goal is None and gxy is None)):
+            raise IrmError("the first plan() needs start and goal (or goal_xy)")
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if self.calls == 0 and goal is None:  # no goal configuration yet: the IK seed of the targets
+            self.context.ik_seed_dev(self.start.data_ptr(), self.goal_xy.data_ptr(), B, self.goal.data_ptr(), 0,
+                                     s.cuda_stream)
         if O and obs is not None:
             self._put(self.obstacles, obs.reshape(-1, 2), self.obstacles.shape)
         if O and vel is not None:
@@ -126,8 +152,7 @@ class Replanner:
                        obstacle_stride=2 * O if self.per_problem else 0, batch=B, alpha_out=a_out.data_ptr(),
                        traj_out=self.traj.data_ptr(), stats_out=self.stats.data_ptr(),
                        obstacle_velocity=self.velocity.data_ptr() if self.moving else 0)
-        s = stream if stream is not None else torch.cuda.current_stream(self.device)
-        self.context.optimize_dev(bd, s.cuda_stream)
+        self.context.optimize_dev(bd, s.cuda_stream, goal_xy_dev=self.goal_xy.data_ptr() if self.task else 0)
         self.cur ^= 1
         self.planned = True
         self.calls += 1

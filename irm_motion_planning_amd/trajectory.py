@@ -12,7 +12,9 @@ meaning; every method runs a HIP kernel through the C ABI:
   compute_trajectory_cost_g   trajectory.py:284-297 irm_eval_cost_grad
   constraintsFulfilled        trajectory.py:129-137 irm_constraints
   constraintsFulfilledVerbose trajectory.py:140-180 irm_constraints (report)
-All methods also accept a leading batch dimension.
+All methods also accept a leading batch dimension.  The cost and constraint methods take an optional goal_xy
+((B×)2): row N−1 is then held to that end-effector target instead of goal_config (irm_*_task; no reference
+counterpart).
 """
 import numpy as np
 
@@ -95,22 +97,24 @@ class Trajectory:
 
     # ----------------------------------------------------------------- costs
     def compute_trajectory_cost(self, alpha, obstacles, start_config, goal_config, lambda_sg_constraint,
-                                lambda_jl_constraint, lambda_max_cost):
+                                lambda_jl_constraint, lambda_max_cost, goal_xy=None):
         return self.context.eval_cost(alpha, obstacles, start_config, goal_config, lambda_sg_constraint,
-                                      lambda_jl_constraint, lambda_max_cost)
+                                      lambda_jl_constraint, lambda_max_cost, goal_xy=goal_xy)
 
     def compute_trajectory_cost_g(self, alpha, obstacles, start_config, goal_config, lambda_sg_constraint,
-                                  lambda_jl_constraint, lambda_max_cost):
+                                  lambda_jl_constraint, lambda_max_cost, goal_xy=None):
         return self.context.eval_cost_grad(alpha, obstacles, start_config, goal_config, lambda_sg_constraint,
-                                           lambda_jl_constraint, lambda_max_cost)
+                                           lambda_jl_constraint, lambda_max_cost, goal_xy=goal_xy)
 
     # ----------------------------------------------------------- constraints
-    def constraintsFulfilled(self, alpha, start_config, goal_config):
-        ok, _ = self.context.constraints(alpha, start_config, goal_config)
+    def constraintsFulfilled(self, alpha, start_config, goal_config, goal_xy=None):
+        ok, _ = self.context.constraints(alpha, start_config, goal_config, goal_xy=goal_xy)
         return ok
 
-    def constraintsFulfilledVerbose(self, alpha, start_config, goal_config, verbose=True):
-        ok, r = self.context.constraints(alpha, start_config, goal_config)
+    def constraintsFulfilledVerbose(self, alpha, start_config, goal_config, verbose=True, goal_xy=None):
+        """With goal_xy the second number of the start/goal position line is the Cartesian distance
+        ‖f(τ_{N−1}) − p‖ of the end effector from its target."""
+        ok, r = self.context.constraints(alpha, start_config, goal_config, goal_xy=goal_xy)
         r = np.asarray(r, np.float32)
         f32 = np.float32
         if verbose:

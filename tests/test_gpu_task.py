@@ -1,0 +1,426 @@
+"""End-effector goals on the GPU: row N−1 is held to a Cartesian target through the end-effector FK and its
+Jacobian instead of to a goal configuration (include/irm.h, "End-effector goals"), and irm_ik_seed.
+
+The yardstick is the fp64 restatement of tests/task_cases.py (checked on the CPU by tests/test_task_host.py)
+plus bit-identity: goal_xy = NULL is the existing call.  Shapes: N = 33 (DynShape, support times n/32 exact in
+fp32), N = 64 at D = 3 (a shape the static dispatch gives to k_lean), D = 7 at N = 40 (moving_cases.LINKS7);
+O = 11 and one case with O = 13; B = 6 (a ragged last workgroup).
+"""
+import numpy as np
+import pytest
+
+import moving_cases as mc
+import task_cases as tc
+from conftest import START, obstacles, params, ref_args
+
+pytestmark = pytest.mark.gpu
+
+ORACLE_FLOOR = 5e-3  # the project's band floor for device-vs-restatement iterates (tests/test_gpu_moving.py)
+GD = ("--optimizer-name", "gd", "--max-outer-iteration", "1", "--loop-loss-reduction=-1e30")
+GD20 = GD + ("--max-inner-iteration", "20")
+BLS1 = ("--optimizer-name", "bls", "--max-outer-iteration", "1", "--max-inner-iteration", "10")
+SHAPES = [(33, 3), (64, 3), (40, 7)]
+
+
+def ctx(*argv, **overrides):
+    from irm_motion_planning_amd.context import Context
+    return Context(params(*argv, **overrides))
+
+
+def links_of(c):
+    return [c.params.link_length[i] for i in range(c.D)]
+
+
+def problems(B, D, seed):
+    rng = np.random.default_rng(seed)
+    return (rng.uniform(-0.5, 0.5, (B, D)).astype(np.float32), rng.uniform(0.2, 1.6, (B, D)).astype(np.float32))
+
+
+def targets_near(links, g, seed):
+    """One target per goal configuration: its FK moved by up to 0.3 per coordinate (fp32, B×2)."""
+    rng = np.random.default_rng(500 + seed)
+    return (tc.fk64(links, g) + rng.uniform(-0.3, 0.3, (len(g), 2))).astype(np.float32)
+
+
+def assert_same_run(x, y):
+    """(alpha, traj, stats) of two optimize() calls, bit for bit, every irm_stats field."""
+    np.testing.assert_array_equal(x[0], y[0])
+    np.testing.assert_array_equal(x[1], y[1])
+    assert set(x[2]) == set(y[2])
+    for k in x[2]:
+        np.testing.assert_array_equal(x[2][k], y[2][k], err_msg=k)
+
+
+# ------------------------------------------------------------------ 1. goal_xy = NULL changes nothing
+def _optimize_task_null(c, s, g, obs):
+    """irm_optimize_batch_task with obstacle_velocity = goal_xy = NULL, as Context.optimize marshals it."""
+    from irm_motion_planning_amd._abi import IrmStats, check
+    from irm_motion_planning_amd.context import _ptr, stats_to_dict
+    B = s.shape[0]
+    alpha = np.zeros((B, c.N, c.D), np.float32)
+    traj = np.zeros_like(alpha)
+    stats = (IrmStats * B)()
+    check(c.lib.irm_optimize_batch_task(c._h, None, _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], 0, B, _ptr(alpha),
+                                        _ptr(traj), stats, None, None, None))
+    return alpha, traj, stats_to_dict(stats)
+
+
+@pytest.mark.parametrize("N,D", SHAPES)
+def test_null_goal_xy_changes_nothing(N, D):
+    from irm_motion_planning_amd import _abi
+    from irm_motion_planning_amd._abi import check
+    from irm_motion_planning_amd.context import _ptr
+    B, O = 6, 11
+    shape = mc.shape_argv(N, D)
+    s, g = problems(B, D, 3 + N)
+    c = ctx(*GD20, *shape)
+    reach = float(sum(links_of(c)))
+    obs = mc.crossing_tables(1, O, 0.8 * reach, seed=N)[0][0]
+    a0 = c.init_alpha(s, g)
+    for lam in ((0.5, 0.1, 0.5), (50, 10, 1.0)):
+        cost = np.zeros(B, np.float32)
+        check(c.lib.irm_eval_cost_task(c._h, _ptr(a0), _ptr(s), _ptr(g), _ptr(obs), O, B, *map(float, lam), _ptr(cost),
+                                       None, None))
+        np.testing.assert_array_equal(cost, c.eval_cost(a0, obs, s, g, *lam))
+        grad, cost2 = np.zeros_like(a0), np.zeros(B, np.float32)
+        check(c.lib.irm_eval_cost_grad_task(c._h, _ptr(a0), _ptr(s), _ptr(g), _ptr(obs), O, B, *map(float, lam),
+                                            _ptr(grad), _ptr(cost2), None, None))
+        Gs, cs = c.eval_cost_grad(a0, obs, s, g, *lam, with_cost=True)
+        np.testing.assert_array_equal(grad, Gs)
+        np.testing.assert_array_equal(cost2, cs)
+    ok, rep = np.zeros(B, np.uint8), np.zeros((B, 11), np.float32)
+    check(c.lib.irm_constraints_task(c._h, _ptr(a0), _ptr(s), _ptr(g), B, ok.ctypes.data_as(_abi.c_uint8_p), _ptr(rep), None))
+    ok0, rep0 = c.constraints(a0, s, g)
+    np.testing.assert_array_equal(ok.astype(bool), ok0)
+    np.testing.assert_array_equal(rep, rep0)
+    # λsg = 0: the goal does not enter, whichever space it is expressed in
+    p = targets_near(links_of(c), g, N)
+    Gt, ct = c.eval_cost_grad(a0, obs, s, g, 0.0, 0.1, 0.25, with_cost=True, goal_xy=p)
+    Gj, cj = c.eval_cost_grad(a0, obs, s, g, 0.0, 0.1, 0.25, with_cost=True)
+    np.testing.assert_allclose(ct, cj, rtol=1e-6, atol=0)
+    np.testing.assert_allclose(Gt, Gj, rtol=1e-6, atol=1e-6 * np.abs(Gj).max())
+    # the optimiser: GD 20 steps and BLS, every irm_stats field; and the launch each of them runs
+    static = c.optimize(s, g, obs)
+    assert np.all(static[2]["grad_evals"] == 20)
+    assert_same_run(_optimize_task_null(c, s, g, obs), static)
+    cb = ctx(*BLS1, *shape)
+    assert_same_run(_optimize_task_null(cb, s, g, obs), cb.optimize(s, g, obs))
+    for cc in (c, cb):
+        assert cc.launch_plan(B, O, goal_xy=None) == cc.launch_plan(B, O)
+    if (N, D) == (64, 3):
+        assert c.launch_plan(B, O)["lean"] == 1  # the static launch stays on k_lean
+
+
+# ------------------------------------------------------------------ 2. cost and gradient against the restatement
+CG_CASES = [(N, D, 0, 11, False) for N, D in SHAPES] + [(33, 3, 1, 11, False), (33, 3, 0, 13, False), (33, 3, 0, 11, True),
+                                                        (40, 7, 1, 11, True)]
+
+
+@pytest.mark.parametrize("lmax", [0.0, 0.25])
+@pytest.mark.parametrize("N,D,whole,O,moving", CG_CASES)
+def test_cost_and_grad_match_the_restatement(N, D, whole, O, moving, lmax):
+    """Bounds of test_gpu_moving.py for a well-conditioned α: cost 1e-5 relative, gradient 2e-4·max|G|.  The
+    joint-goal call meets them on the same α (else the input is wrong, not the feature), and the task and joint
+    results differ by more than 1e-3 relative.  whole = 1 catches a wrong Jacobian on the end row."""
+    B = 3
+    shape = mc.shape_argv(N, D)
+    c = ctx(*shape, whole_robot_cost=whole)
+    R, o = tc.restatement(*shape, whole_robot=bool(whole))
+    alpha, s, g = mc.well_conditioned_alpha(o, B, D, seed=N + D)
+    links = links_of(c)
+    reach = float(sum(links))
+    p, w = mc.crossing_tables(B, O, 0.8 * reach, seed=N)
+    if not moving:
+        w = np.zeros_like(w)
+    # targets well away from where the end rows are (|α| is small: T[N−1] ≈ 0, f ≈ (reach, 0))
+    xy = targets_near(links, g, N + D)
+    lam = (0.5, 0.1, lmax)
+    for b in range(B):
+        tab = R.table(p[b], w[b])
+        vel = w[b] if moving else None
+        goal = tc.TaskGoal(xy[b])
+        ref, Gref = R.cost(alpha[b], tab, s[b], goal, *lam), R.cost_g(alpha[b], tab, s[b], goal, *lam)
+        G, cost = c.eval_cost_grad(alpha[b], p[b], s[b], g[b], *lam, with_cost=True, obstacle_velocity=vel, goal_xy=xy[b])
+        assert cost == c.eval_cost(alpha[b], p[b], s[b], g[b], *lam, obstacle_velocity=vel, goal_xy=xy[b])
+        ref0, Gref0 = R.cost(alpha[b], tab, s[b], g[b], *lam), R.cost_g(alpha[b], tab, s[b], g[b], *lam)
+        G0, cost0 = c.eval_cost_grad(alpha[b], p[b], s[b], g[b], *lam, with_cost=True, obstacle_velocity=vel)
+        print(f"N={N} D={D} whole={whole} O={O} moving={moving} lmax={lmax} b={b}: task cost {cost:.7f} vs {ref:.7f} "
+              f"(rel {abs(cost - ref) / abs(ref):.1e}), |G - ref| {np.abs(G - Gref).max() / np.abs(Gref).max():.1e}·max|G|; "
+              f"joint rel {abs(cost0 - ref0) / abs(ref0):.1e}, {np.abs(G0 - Gref0).max() / np.abs(Gref0).max():.1e}")
+        assert abs(cost0 - ref0) <= 1e-5 * abs(ref0), "the input is wrong, not the feature"
+        assert np.abs(G0 - Gref0).max() <= 2e-4 * np.abs(Gref0).max(), "the input is wrong, not the feature"
+        assert abs(cost - ref) <= 1e-5 * abs(ref), (b, cost, ref)
+        assert np.abs(G - Gref).max() <= 2e-4 * np.abs(Gref).max(), b
+        assert abs(cost0 - cost) > 1e-3 * abs(cost), (cost0, cost)
+        assert np.abs(G0 - G).max() > 1e-3 * np.abs(G).max()
+
+
+# ------------------------------------------------------------------ 3. constraints
+@pytest.mark.parametrize("N,D", [(33, 3), (64, 3)])
+def test_constraints_report_the_cartesian_distance(N, D):
+    """α = init_alpha(s, q) ends at q, so with p = f(q) + (δ, 0) report[1] is δ within 1e-4 (the position error
+    of the fp32 line fit); the start/goal sub-flag (eps_position 0.01) is true at δ = 0.005 and false
+    at δ = 0.02.
+    At N = 64 the line fit itself misses q by more than that (|α| grows with N): the joint-goal report of the
+    same α, e_q = ‖T[N−1] − q‖, measures it, and the end effector is then off by at most ‖J_ee‖·e_q with
+    ‖J_ee‖ ≤ sqrt(Σ_d (Σ_{l≥d} L_l)²); the bound there is 1e-4 + that, still far inside 0.005."""
+    B = 6
+    c = ctx(*mc.shape_argv(N, D))
+    s, q = problems(B, D, 21 + N)
+    a = c.init_alpha(s, q)
+    links = links_of(c)
+    f = tc.fk64(links, q)
+    _, rep0 = c.constraints(a, s, q)
+    jnorm = float(np.sqrt(np.sum(np.cumsum(np.asarray(links, np.float64)[::-1]) ** 2)))
+    bound = 1e-4 if N == 33 else 1e-4 + jnorm * rep0[:, 1].astype(np.float64)
+    for delta, flag in ((0.005, True), (0.02, False)):
+        p = (f + np.array([delta, 0.0])).astype(np.float32)
+        ok, rep = c.constraints(a, s, q, goal_xy=p)
+        print(f"N={N} delta={delta}: report[1] {rep[:, 1]}, joint-goal report[1] {rep0[:, 1]}, bound {bound}")
+        assert np.all(np.abs(rep[:, 1] - delta) <= bound), rep[:, 1]
+        assert np.all(rep[:, 7] == (1.0 if flag else 0.0))
+        assert not ok.any() or flag
+        # everything but the goal distance and its sub-flag is the joint-goal report
+        keep = [0, 2, 3, 4, 5, 6, 8, 9, 10]
+        np.testing.assert_array_equal(rep[:, keep], rep0[:, keep])
+
+
+# ------------------------------------------------------------------ 4. dispatch
+@pytest.mark.parametrize("N", [64, 128])
+def test_task_launch_runs_the_general_kernel(N):
+    c = ctx(*GD20, *mc.shape_argv(N, 3))
+    p = np.zeros((6, 2), np.float32)
+    for B in (6, 1024):
+        task, sta = c.launch_plan(B, 11, goal_xy=p), c.launch_plan(B, 11)
+        assert task["lean"] == 0 and task["kernel"].startswith("k_optimize<DynShape<3>"), task
+        assert sta["lean"] == 1 and sta["kernel"].startswith("k_lean<"), sta
+    # a queued context runs the static launch for such a call
+    cq = ctx(*BLS1, *mc.shape_argv(N, 3))
+    cq.set_work_queue(-1)
+    task = cq.launch_plan(1024, 11, goal_xy=p)
+    assert task["lean"] == 0 and task["kernel"].startswith("k_optimize<DynShape<3>") and task["grid"] * task["traj_per_block"] >= 1024
+
+
+# ------------------------------------------------------------------ 5. GD iterates against the restatement
+@pytest.mark.parametrize("N", [33, 64])
+def test_gd_iterates_match_the_restatement(N):
+    """15 single-loop GD steps, λmax = 0.  The band is measured on the existing code path in the same test:
+    e_static = max |joint-goal device run − Ref64.gd_single|; the task run lies within max(2·e_static, 5e-3) of
+    the task restatement."""
+    B, D, O = 6, 3, 11
+    argv = GD + ("--max-inner-iteration", "15", "--lambda-max-cost", "0") + tuple(mc.shape_argv(N, D))
+    c = ctx(*argv)
+    R, o = tc.restatement(*argv)
+    s, g = problems(B, D, N)
+    p, _ = mc.crossing_tables(B, O, 2.4, seed=N)
+    xy = targets_near(links_of(c), g, N)
+    a0 = c.init_alpha(s, g)
+    _, t_sta, st_sta = c.optimize(s, g, p, alpha0=a0)
+    _, t_task, st_task = c.optimize(s, g, p, alpha0=a0, goal_xy=xy)
+    assert np.all(st_sta["grad_evals"] == 15) and np.all(st_task["grad_evals"] == 15)
+    e_static = e_task = 0.0
+    for b in range(B):
+        a_s, _, n_s = R.gd_single(a0[b], p[b], s[b], g[b], 15)
+        a_t, _, n_t = R.gd_single(a0[b], p[b], s[b], tc.TaskGoal(xy[b]), 15)
+        assert n_s == n_t == 15
+        e_static = max(e_static, float(np.abs(t_sta[b] - R.traj_vel(a_s)[0]).max()))
+        e_task = max(e_task, float(np.abs(t_task[b] - R.traj_vel(a_t)[0]).max()))
+    moved = float(np.abs(t_task - t_sta).max())
+    print(f"N={N}: e_static {e_static:.3e}, task error {e_task:.3e}, band {max(2 * e_static, ORACLE_FLOOR):.3e}; "
+          f"|task plan - joint plan| {moved:.3e}")
+    assert moved > 1e-3  # the target reached the launch
+    assert e_task <= max(2.0 * e_static, ORACLE_FLOOR), (e_task, e_static)
+
+
+# ------------------------------------------------------------------ 5b. every flow and variant minimises the task loss
+FLOWS = {"gd1": GD20, "gd2": ("--optimizer-name", "gd", "--max-outer-iteration", "3", "--max-inner-iteration", "10"),
+         "bls": ("--optimizer-name", "bls", "--max-outer-iteration", "2", "--max-inner-iteration", "10")}
+
+
+@pytest.mark.parametrize("flow", sorted(FLOWS))
+@pytest.mark.parametrize("N,D,whole,moving,series", [(33, 3, 0, False, False), (40, 7, 1, True, False), (33, 3, 0, True, True),
+                                                     (64, 3, 1, False, True)])
+def test_stats_follow_the_task_objective(N, D, whole, moving, series, flow):
+    """GD single loop, GD dual loop and BLS, composed with whole_robot, moving obstacles and series recording:
+    final_loss is the task loss of α_out at the weights of the last inner loop, λ·increase^(outer_iterations − 1)
+    (eval_cost(goal_xy=), 1e-5 relative as in test_gpu_moving.py, for the single loop and BLS).  In the GD dual
+    loop the rounds evaluate a state that lags α by one rounding residual, which the raised
+    weights amplify: joint-goal launches show 2e-5 … 1.5e-4 against their own eval_cost (printed here), so there
+    final_loss only has to be the task loss rather than the joint one — closer to the task cost of α_out than a
+    tenth of the distance between the two costs.  constraints_ok is the task constraint of α_out, the plan
+    differs from the joint-goal plan, the series' first frame is α0's trajectory, traj_out = K·α_out·J."""
+    B, O = 3, 11
+    c = ctx(*FLOWS[flow], *mc.shape_argv(N, D), whole_robot_cost=whole)
+    pr = c.params
+    s, g = problems(B, D, 3 * N)
+    links = links_of(c)
+    p, w = mc.crossing_tables(1, O, 0.8 * float(sum(links)), seed=D)
+    p, w = p[0], (w[0] if moving else None)
+    xy = targets_near(links, g, N)
+    a0 = c.init_alpha(s, g)
+    res = c.optimize(s, g, p, alpha0=a0, obstacle_velocity=w, goal_xy=xy, series=series)
+    alpha, traj, st = res[:3]
+
+    def loss_gap(alpha, st, goal_xy):
+        """|final_loss − eval_cost(α_out)| / eval_cost at the last inner loop's weights, per problem."""
+        gap, apart = np.zeros(B), np.zeros(B)
+        for b in range(B):
+            lsg, ljl = np.float32(pr.lambda_sg_constraint), np.float32(pr.lambda_jl_constraint)
+            for _ in range(int(st["outer_iterations"][b]) - 1):  # fp32, as the kernel raises them
+                lsg, ljl = lsg * np.float32(pr.lambda_constraint_increase), ljl * np.float32(pr.lambda_constraint_increase)
+            ref = float(c.eval_cost(alpha[b], p, s[b], g[b], lsg, ljl, pr.lambda_max_cost, obstacle_velocity=w,
+                                    goal_xy=None if goal_xy is None else goal_xy[b]))
+            gap[b] = abs(float(st["final_loss"][b]) - ref) / abs(ref)
+            other = float(c.eval_cost(alpha[b], p, s[b], g[b], lsg, ljl, pr.lambda_max_cost, obstacle_velocity=w,
+                                      goal_xy=xy[b] if goal_xy is None else None))
+            apart[b] = abs(other - ref) / abs(ref)
+        return gap, apart
+
+    a_j, joint, st_j = c.optimize(s, g, p, alpha0=a0, obstacle_velocity=w)
+    (gap_task, apart), (gap_joint, _) = loss_gap(alpha, st, xy), loss_gap(a_j, st_j, None)
+    print(f"N={N} D={D} whole={whole} moving={moving} series={series} {flow}: final_loss {st['final_loss']}, relative gap to "
+          f"eval_cost: task {gap_task}, joint goal {gap_joint}; task and joint cost of alpha_out apart by {apart}; "
+          f"outer {st['outer_iterations']}, ok {st['constraints_ok']}")
+    if flow == "gd2":
+        assert np.all(gap_task <= 0.1 * apart), (gap_task, apart)
+    else:
+        assert np.all(gap_task <= 1e-5), gap_task
+    ok, _ = c.constraints(alpha, s, g, goal_xy=xy)
+    np.testing.assert_array_equal(ok, st["constraints_ok"].astype(bool))
+    np.testing.assert_array_equal(traj, c.evaluate(alpha))
+    assert np.abs(joint - traj).max() > 1e-3  # the target reached the launch
+    if series:
+        np.testing.assert_array_equal(res[3][:, 0], c.evaluate(a0))
+        assert np.all(st["series_len"] >= 2)
+
+
+# ------------------------------------------------------------------ 6. end to end: BLS, default hyper-parameters
+@pytest.mark.parametrize("N", tc.E2E_N)
+def test_end_to_end_bls_reaches_the_targets(N):
+    """The reference arm and obstacles, start 0, goal=None (the IK seed), default hyper-parameters: every problem
+    ends with constraints_ok, an independent fp64 FK of traj_out[N−1] lies within eps_position + 1e-4 of the
+    target (1e-4: the fp32 waypoint error), and constraints(goal_xy=) on α_out agrees with the flag.
+    The fp64 restatement reaches ok on the same problems from the seed and from perturbed seeds
+    (tests/test_task_host.py)."""
+    c = ctx("--n-timesteps", N)
+    xy = tc.E2E_TARGETS
+    B = len(xy)
+    s = np.tile(START, (B, 1))
+    alpha, traj, st = c.optimize(s, None, obstacles(), goal_xy=xy)
+    f = tc.fk64(links_of(c), traj[:, -1])
+    dist = np.linalg.norm(f - xy.astype(np.float64), axis=1)
+    q, _ = c.ik_seed(s, xy)
+    ok, rep = c.constraints(alpha, s, q, goal_xy=xy)
+    print(f"N={N}: constraints_ok {st['constraints_ok']}, outer {st['outer_iterations']}, inner {st['inner_iterations']}, "
+          f"|f(traj[N-1]) - p| {dist}, report[1] {rep[:, 1]}")
+    assert np.all(st["constraints_ok"] == 1), st
+    assert np.all(dist < float(c.params.eps_position) + 1e-4), dist
+    np.testing.assert_array_equal(ok, st["constraints_ok"].astype(bool))
+
+
+# ------------------------------------------------------------------ 7. ik_seed
+def test_ik_seed():
+    from irm_motion_planning_amd._abi import IrmError
+    c3 = ctx("--n-timesteps", 33)
+    lo, hi = tc.safety_range(c3.params)
+    links = links_of(c3)
+    q, res = c3.ik_seed(START, tc.IK_TARGETS3)  # one start, several targets
+    print("3-DoF residuals", res)
+    assert q.shape == (4, 3) and res.shape == (4,)
+    true = np.linalg.norm(tc.fk64(links, q) - tc.IK_TARGETS3.astype(np.float64), axis=1)
+    assert np.all(np.abs(res - true) <= 1e-5) and np.all(res < 1e-4)
+    assert q.min() >= lo and q.max() <= hi
+    c7 = ctx(*mc.shape_argv(40, 7))
+    s7, p7 = tc.ik_problems7()
+    q7, r7 = c7.ik_seed(s7, p7)
+    print("7-DoF residuals", r7)
+    true7 = np.linalg.norm(tc.fk64(mc.LINKS7, q7) - p7.astype(np.float64), axis=1)
+    assert np.all(np.abs(r7 - true7) <= 1e-5) and np.all(r7 < 1e-4)
+    assert q7.min() >= lo and q7.max() <= hi
+    # a problem's result does not depend on its batch: B = 1 against B = 6, bit for bit
+    q6, r6 = c7.ik_seed(s7[:6], p7[:6])
+    for b in range(6):
+        q1, r1 = c7.ik_seed(s7[b], p7[b])
+        np.testing.assert_array_equal(q1, q6[b])
+        assert r1 == r6[b]
+    np.testing.assert_array_equal(q6, q7[:6])
+    # beyond the reach: IRM_OK, the residual is the missing length
+    start, far = tc.out_of_reach(links)
+    _, rfar = c3.ik_seed(start, far)
+    assert abs(float(rfar) - 1.0) <= 1e-3
+    # behind the joint limits: best effort, inside the range, the residual it reports is the true one
+    qb, rb = c3.ik_seed(START, np.array([-2.0, -1.5], np.float32))
+    assert qb.min() >= lo and qb.max() <= hi
+    assert abs(float(rb) - np.linalg.norm(tc.fk64(links, qb) - np.array([-2.0, -1.5]))) <= 1e-5
+    for bad in (np.nan, np.inf):
+        with pytest.raises(IrmError, match="not finite"):
+            c3.ik_seed(START, np.array([bad, 1.0], np.float32))
+        with pytest.raises(IrmError, match="not finite"):
+            c3.optimize(START, START, obstacles(), goal_xy=np.array([1.0, bad], np.float32))
+        with pytest.raises(IrmError, match="not finite"):
+            c3.eval_cost(c3.init_alpha(START, START), obstacles(), START, START, 0.5, 0.1, 0.5,
+                         goal_xy=np.array([bad, bad], np.float32))
+
+
+# ------------------------------------------------------------------ 8. Replanner
+def test_replanner_goal_xy():
+    from irm_motion_planning_amd.replanning import Replanner
+    argv = ("--n-timesteps", "33")
+    args = ref_args(*argv)
+    xy = tc.E2E_TARGETS
+    B, O = len(xy), 11
+    s = np.tile(START, (B, 1))
+    obs = obstacles()
+    rp = Replanner(args, batch=B, n_obstacles=O)
+    c = ctx(*argv)
+    st1 = rp.plan(obs, s, goal_xy=xy)  # no goal configuration: the IK seed, on the device
+    a1, t1, st_h = c.optimize(s, None, obs, goal_xy=xy)
+    np.testing.assert_array_equal(rp.alpha_host(), a1)
+    np.testing.assert_array_equal(rp.trajectory_host(), t1)
+    np.testing.assert_array_equal(st1["final_loss"], st_h["final_loss"])
+    np.testing.assert_array_equal(rp.goal.cpu().numpy(), c.ik_seed(s, xy)[0])
+    assert np.all(st1["constraints_ok"] == 1)
+    # the second plan starts from the first's α and ends ok
+    st2 = rp.plan(obs, goal_xy=xy, warm_start=True)
+    a2, t2, st2_h = c.optimize(s, c.ik_seed(s, xy)[0], obs, alpha0=a1, goal_xy=xy)
+    np.testing.assert_array_equal(rp.alpha_host(), a2)
+    np.testing.assert_array_equal(st2["inner_iterations"], st2_h["inner_iterations"])
+    assert np.all(st2["constraints_ok"] == 1)
+    # a plan() without goal_xy re-uses the table (still a task plan: the same call once more from a2)
+    rp.plan(obs)
+    a3, _, _ = c.optimize(s, c.ik_seed(s, xy)[0], obs, alpha0=a2, goal_xy=xy)
+    np.testing.assert_array_equal(rp.alpha_host(), a3)
+    assert rp.task
+    # advance() carries the table: the target is a point of the world
+    rp.advance(0.25)
+    rp.torch.cuda.synchronize()
+    np.testing.assert_array_equal(rp.goal_xy.cpu().numpy(), xy)
+    rp.plan()
+    assert rp.task
+    # a goal configuration alone goes back to the joint goal
+    rp.plan(obs, s, c.ik_seed(s, xy)[0], warm_start=False)
+    assert not rp.task
+    np.testing.assert_array_equal(rp.trajectory_host(), c.optimize(s, c.ik_seed(s, xy)[0], obs)[1])
+
+
+# ------------------------------------------------------------------ 9. CLI
+CLI = ["--max-outer-iteration", "2", "--max-inner-iteration", "10", "--n-timesteps", "33"]
+
+
+def test_cli_goal_xy(tmp_path, monkeypatch):
+    from irm_motion_planning_amd import main as irm_main
+    out = {}
+    for tag, extra in (("none", []), ("task", ["--goal-xy", "1.348", "2.538"])):
+        d = tmp_path / tag
+        d.mkdir()
+        monkeypatch.chdir(d)
+        irm_main.main(CLI + extra)
+        out[tag] = (d / "trajectory_result.txt").read_bytes()
+    assert out["task"] != out["none"]
+    for tag, extra in (("bnone", []), ("btask", ["--goal-xy", "1.348", "2.538"])):
+        d = tmp_path / tag
+        d.mkdir()
+        monkeypatch.chdir(d)
+        irm_main.main(CLI + ["--batch-size", "5"] + extra)
+        out[tag] = {f.name: f.read_bytes() for f in sorted(d.iterdir())}
+    assert out["btask"]["trajectory_result_batch.txt"] != out["bnone"]["trajectory_result_batch.txt"]
