@@ -626,6 +626,10 @@ struct EvalOut {
 // Wave-reduce this lane's waypoint terms; lane 0 of each wave stores the
 // partials, the lanes of rows 0 / N−1 store the start/goal terms.  Must be
 // reached by the whole wave (a wave never straddles two trajectories).
+// kRedW: words per wave of `red`, the eight partials — plan_head gives the region kMaxWaves·8 words and `sg`
+// follows it directly, so a wider stride would put the partials of a 1024-thread workgroup's last waves onto
+// the start/goal words (four N = 256 or two N = 512 trajectories in one workgroup).
+constexpr int kRedW = 8;
 template <int D>
 __device__ __forceinline__ void eval_partials(const KParams& P, bool live, const WP<D>& w, int n, int wave,
                                               const float (&q)[D], const float (&v)[D], const float (&s)[D],
@@ -642,7 +646,7 @@ __device__ __forceinline__ void eval_partials(const KParams& P, bool live, const
     const float tn = wred_min(live ? w.tn : INFINITY);
     const float va = wred_max(live ? w.va : 0.f);
     if ((threadIdx.x & 63) == 0) {
-        float* r = red + wave * 10;
+        float* r = red + wave * kRedW;
         r[0] = cmax;
         r[1] = __int_as_float(cidx);
         r[2] = csum;
@@ -669,12 +673,12 @@ __device__ __forceinline__ void eval_partials(const KParams& P, bool live, const
 // Combine the trajectory's wave partials (fixed order) into loss + stats.
 __device__ __forceinline__ EvalOut eval_finalize(const KParams& P, const float* red, const float* sg, int t,
                                                  int wave0, int nwt, float lsg, float ljl) {
-    const float* r = red + wave0 * 10;
+    const float* r = red + wave0 * kRedW;
     float cmax = r[0];
     int cidx = __float_as_int(r[1]);
     float csum = r[2], jps = r[3], jvs = r[4], tx = r[5], tn = r[6], va = r[7];
     for (int w = 1; w < nwt; ++w) {
-        const float* q = red + (wave0 + w) * 10;
+        const float* q = red + (wave0 + w) * kRedW;
         amax_step(cmax, cidx, q[0], __float_as_int(q[1]));
         csum += q[2];
         jps += q[3];
@@ -1751,7 +1755,10 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
             __syncthreads();
             if (rs && valid) {
                 eval_exact<D>(P, X + t * D, n, q, v, cold_ptr(2), cold_ptr(3));
-                if (rec && st.series_len > 0) {
+                // the last extended-vis frame shows the exact trajectory of this α — but frame 0 stays the
+                // initial trajectory: a BLS inner loop that ends on its first, accepted step has moved α
+                // without a snapshot (optimizer_BLS.py:97-107)
+                if (rec && st.series_len > 1) {
                     float* ser = cold_ptr(0);
                     const int ms = cold_int(C_MAXSER);
 #pragma unroll
@@ -4060,8 +4067,9 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                     if (vl[j]) {
                         if constexpr (D <= 3) eval_exact<D, kResyncU, true>(P, X + (t * D) * ldx, nn[j], q[j], v[j], nullptr, nullptr, 1, ldx, Jl);
                         else eval_exact_loop<D, 4>(P, X + (t * D) * ldx, ldx, nn[j], N, Jl, q[j], v[j]);
-                        // the last extended-vis frame shows the exact trajectory of the returned α
-                        if (rec && st.series_len > 0) {
+                        // the last extended-vis frame shows the exact trajectory of the returned α (frame 0
+                        // stays the initial trajectory, as in k_optimize)
+                        if (rec && st.series_len > 1) {
 #pragma unroll
                             for (int k = 0; k < D; ++k)
                                 P.series[((b * P.max_series) + st.series_len - 1) * N * D + ser_row(j) + k] = q[j][k];

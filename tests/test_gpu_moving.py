@@ -6,6 +6,7 @@ tests/test_moving_host.py) plus bit-identity: a zero velocity changes nothing, a
 the static dense_check against the table frozen at p + τ·w.  Shapes: N = 33 (DynShape, support times n/32
 exact in fp32), N = 64 at D = 3 (a shape the static dispatch gives to k_lean), D = 7 at N = 40;
 O ∈ {5, 11, 13} (the 9-12-obstacle block, the pair loop, sentinel padding); B = 6 (a ragged last workgroup).
+N > 64 (a trajectory over several waves) and TB > 1 (several problems per workgroup): tests/test_gpu_variant_shapes.py.
 """
 import numpy as np
 import pytest

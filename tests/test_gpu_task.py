@@ -5,6 +5,7 @@ The yardstick is the fp64 restatement of tests/task_cases.py (checked on the CPU
 plus bit-identity: goal_xy = NULL is the existing call.  Shapes: N = 33 (DynShape, support times n/32 exact in
 fp32), N = 64 at D = 3 (a shape the static dispatch gives to k_lean), D = 7 at N = 40 (moving_cases.LINKS7);
 O = 11 and one case with O = 13; B = 6 (a ragged last workgroup).
+N > 64 (a trajectory over several waves) and TB > 1 (several problems per workgroup): tests/test_gpu_variant_shapes.py.
 """
 import numpy as np
 import pytest
