@@ -68,28 +68,31 @@ __global__ void k_fk_joints(KParams P, const float* traj, float* pos) {
     }
 }
 
-// environment.py:32-58 for B×N points (shared obstacles).
+// environment.py:32-58 for B×N points (shared obstacles).  Each obstacle's term and the three sums are formed in
+// fp64 from the fp32 inputs and rounded once: the gradient of a point among many obstacles is a sum of terms of
+// magnitude up to 1 that cancel, and an fp32 sum of them (half an ulp of 1 per addition, 3 ulp per term through
+// v_rcp_f32) misses the host API's elementwise bound rtol 1e-5 + atol 1e-7 from 8 obstacles on
+// (tests/test_gpu_physics.py, test_obstacle_counts_cost_vg).  Not a hot path: one launch per host call.
 __global__ void k_cost_vg(KParams P, const float* f, float* cv_out, float* cg_out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int N = P.N;
     if (i >= P.B * N) return;
     const int b = i / N, n = i - b * N;
-    const float fx = f[(size_t)b * 2 * N + n], fy = f[(size_t)b * 2 * N + N + n];
-    float cv = 0.f, ax = 0.f, ay = 0.f;
+    const double fx = f[(size_t)b * 2 * N + n], fy = f[(size_t)b * 2 * N + N + n];
+    double cv = 0.0, ax = 0.0, ay = 0.0;
     for (int o = 0; o < P.O; ++o) {
-        const float dx = fx - P.obstacles[2 * o], dy = fy - P.obstacles[2 * o + 1];
-        const float r2 = dx * dx + dy * dy;
-        const float den = 0.5f + 0.5f * r2;
-        const float inv = __builtin_amdgcn_rcpf(den);
-        cv += 0.8f * inv;
-        const float i2 = inv * inv;
-        ax += (-0.8f * dx) * i2;
-        ay += (-0.8f * dy) * i2;
+        const double dx = fx - (double)P.obstacles[2 * o], dy = fy - (double)P.obstacles[2 * o + 1];
+        const double r2 = dx * dx + dy * dy;
+        const double inv = 1.0 / (0.5 + 0.5 * r2);
+        cv += 0.8 * inv;
+        const double i2 = inv * inv;
+        ax += (-0.8 * dx) * i2;
+        ay += (-0.8 * dy) * i2;
     }
-    cv_out[i] = cv;
+    cv_out[i] = (float)cv;
     if (cg_out) {
-        cg_out[(size_t)b * 2 * N + n] = ax;
-        cg_out[(size_t)b * 2 * N + N + n] = ay;
+        cg_out[(size_t)b * 2 * N + n] = (float)ax;
+        cg_out[(size_t)b * 2 * N + N + n] = (float)ay;
     }
 }
 

@@ -186,7 +186,9 @@ __device__ __forceinline__ void store_tile(float* out, int tile, f32x4 acc, unsi
 // ------------------------------------------------ per-waypoint physics
 // sin/cos for robot.py's joint angles: Cody-Waite reduction by π/2 (3-part
 // split, fma) and the cephes single-precision minimax polynomials on
-// [−π/4, π/4]; ≈1 ulp, branch-free.  |x| > 1e4 rad falls back to sincosf.
+// [−π/4, π/4]; branch-free.  Measured against double for |x| ≤ 1e4 (tests/test_physics_host.py, 1.1e8
+// angles): at most 1.56 ulp of the correctly rounded result, for sin and for cos, next to odd multiples of
+// π/4 (1.3 / 1.4 ulp next to multiples of π/2); asserted < 2 ulp.  |x| > 1e4 rad falls back to sincosf.
 __device__ __forceinline__ void sincos_poly(float x, float& sn, float& cs) {
     // k = round(x·2/π) by the 1.5·2²³ shifter: one fma rounds the exact product to an integer (ties to
     // even), whose low bits are k's two's-complement bits in t's mantissa (|k| < 2²² here); kf = k as a
