@@ -464,6 +464,79 @@ int irm_ik_seed(irm_ctx* ctx, const float* start, const float* goal_xy, int32_t 
 int irm_ik_seed_dev(irm_ctx* ctx, const float* start_dev, const float* goal_xy_dev, int32_t batch, float* q_dev,
                     float* residual_dev, void* stream);
 
+/* Via-points: hold interior support rows to joint or Cartesian targets.  A call may carry V via-points,
+ * 1 ≤ V ≤ IRM_MAX_VIA.  Via-point v names a support row m_v (strictly increasing, each in [1, N−2]) and a kind;
+ * the row table and the kinds are shared by the batch (a row is a via row for every problem), the targets are
+ * per problem: target is B×V×D fp32.  A joint via-point (cartesian = 0) uses all D values c; an end-effector
+ * via-point (cartesian = 1, D ≥ 2) uses the first two values p and ignores the rest.  Three places change,
+ * nothing else:
+ *   loss         += λsg · ½ · Σ_v r_v²
+ *   a[m_v]       += λsg · ge_v            (position gradient input of row m_v only)
+ *   constraints  :  ok  &=  sqrtf(r_v²) < eps_position   for every v
+ * Joint:        e[d] = T[m_v][d] − c[d], ge_v = e, r_v² = Σ_d e[d]² accumulated as the same kernel accumulates
+ *               row N−1 against `goal` (cost / gradient / constraints: a += e·e; the optimiser: fmaf(e, e, a)).
+ * End effector: e = f(T[m_v]) − p, r_v² = fmaf(e_y, e_y, e_x·e_x), ge_v[d] = fmaf(J_y[d], e_y, J_x[d]·e_x) — the
+ *               end-effector-goal order above, f and J_ee from the waypoint's own evaluation (no second FK);
+ *               J_ee is the end effector's also with whole_robot_cost = 1.
+ * The velocity of a via row is free: no term enters b, and the sparse-velocity logic of the optimiser keeps seeing
+ * only rows 0 and N−1 — the robot passes through a via-point, it does not stop there (chaining two plans would).
+ * fp32 order of the loss: the via terms join the start/goal position sum in index order after the existing two,
+ *   cost / gradient / constraints:  s = 0.5·a0 + 0.5·a1;           then for v = 0 … V−1:  s = s + 0.5·r_v²
+ *   the optimiser:                  s = fmaf(0.5, a0, 0.5·a1);     then for v = 0 … V−1:  s = fmaf(0.5, r_v², s)
+ * and λsg·ge_v[d] enters a[m_v][d] where λsg·(T[N−1] − g)[d] enters a[N−1][d] (one fmaf onto the obstacle term).
+ * λsg is the call's or round's current value: the dual loop and BLS escalate it with the rest until eps_position
+ * holds.  irm_stats.final_loss and constraints_ok follow the via loss and the via constraint.  Via-points compose
+ * with goal_xy, obstacle_velocity (both stay nullable: the _via forms are the superset of the _task forms),
+ * whole_robot_cost, per-problem obstacle tables and series recording.
+ * via = NULL or n_via = 0 is the existing call: the same dispatch and the same bits as the _task entry point
+ * (including which launches stay on the shape-specialised k_lean kernels and on the work queue).  A via launch
+ * runs the general kernel k_optimize<DynShape<D>>, every flow, as moving and end-effector-goal launches do;
+ * k_lean and the work queue have no via variant (a queued context runs the static launch for such a call).  The
+ * via words r_v² take IRM_MAX_VIA floats of LDS per trajectory of a workgroup; a shape that no longer fits is
+ * IRM_EINVAL.
+ * IRM_EINVAL (with a message): V outside [0, IRM_MAX_VIA]; a row outside [1, N−2] or rows not strictly
+ * increasing; a cartesian value other than 0 or 1; a Cartesian via-point at D = 1; a NULL target with V > 0; in
+ * the host-pointer forms a non-finite value among the target entries that are read (D per joint via-point, 2 per
+ * end-effector one).  The _dev form cannot see the values.
+ * Additive symbols: IRM_ABI_VERSION stays 3 and no struct changes layout; no reference counterpart. */
+#define IRM_MAX_VIA 4
+typedef struct irm_via {
+    int32_t n_via;
+    int32_t row[IRM_MAX_VIA];        /* strictly increasing, each in [1, N−2] */
+    int32_t cartesian[IRM_MAX_VIA];  /* 0 joint target, 1 end-effector target */
+    const float* target;             /* B×V×D (host pointer; device pointer in the _dev form) */
+} irm_via;
+int irm_eval_cost_via(irm_ctx* ctx, const float* alpha, const float* start, const float* goal,
+                      const float* obstacles, int32_t n_obstacles, int32_t batch,
+                      float lambda_sg, float lambda_jl, float lambda_max, float* cost_out,
+                      const float* obstacle_velocity, const float* goal_xy, const irm_via* via);
+int irm_eval_cost_grad_via(irm_ctx* ctx, const float* alpha, const float* start, const float* goal,
+                           const float* obstacles, int32_t n_obstacles, int32_t batch,
+                           float lambda_sg, float lambda_jl, float lambda_max,
+                           float* grad_out, float* cost_out, const float* obstacle_velocity,
+                           const float* goal_xy, const irm_via* via);
+/* via_dist_out: B×V, nullable, sqrtf(r_v²).  The 11-float report is the _task form's; ok_out includes the via
+ * flags. */
+int irm_constraints_via(irm_ctx* ctx, const float* alpha, const float* start, const float* goal, int32_t batch,
+                        uint8_t* ok_out, float* report_out, const float* goal_xy, const irm_via* via,
+                        float* via_dist_out);
+int irm_optimize_batch_via(irm_ctx* ctx, const float* alpha0, const float* start, const float* goal,
+                           const float* obstacles, int32_t n_obstacles, int32_t obstacle_stride,
+                           int32_t batch, float* alpha_out, float* traj_out, irm_stats* stats_out,
+                           float* series_out, const float* obstacle_velocity, const float* goal_xy,
+                           const irm_via* via);
+/* Device pointers, enqueue-only on `stream`; via->target is a device pointer, args->batch × V × D (the struct
+ * itself is read on the host, during the call). */
+int irm_optimize_batch_via_dev(irm_ctx* ctx, const irm_batch_dev* args, const float* obstacle_velocity_dev,
+                               const float* goal_xy_dev, void* stream, const irm_via* via);
+/* irm_optimize_plan for a via launch of the same arguments: the kernel such a launch runs.  Only n_via, row and
+ * cartesian are read (target may be NULL); via = NULL is irm_optimize_plan_task.  Like irm_optimize_plan_task it
+ * takes no velocity table: it describes the launch with static obstacles.  A via launch that also carries
+ * obstacle_velocity runs the same kernel with the second obstacle table in LDS, so its lds_bytes is larger and,
+ * where that no longer fits, its traj_per_block smaller than reported here. */
+int irm_optimize_plan_via(const irm_ctx* ctx, int32_t batch, int32_t n_obstacles, int32_t record_series,
+                          irm_launch_plan* out, const irm_via* via);
+
 /* Build id of the library: the first 16 hex digits of the SHA-256 over every file of
  * irm_motion_planning_amd/csrc and include/irm.h, the compile flags of every unit and the build
  * variant (build.py source_hash); "unknown" otherwise.

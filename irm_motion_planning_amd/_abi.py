@@ -8,6 +8,8 @@ the calls raise IrmError.
 import ctypes
 import os
 
+from . import via as _via  # irm_via's mirror lives with the via-point value object
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IRM_LIB") or os.path.join(HERE, "libirm_hip.so")
 
@@ -289,6 +291,38 @@ PROTOTYPES = {
     "irm_ik_seed": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, c_float_p, c_float_p]),
     "irm_ik_seed_dev": (
         ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, c_float_p, c_float_p, ctypes.c_void_p]
+    ),
+    # via-points: the _task twins' arguments plus a trailing irm_via* (NULL: the existing call)
+    "irm_eval_cost_via": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_float, ctypes.c_float, ctypes.c_float, c_float_p, c_float_p, c_float_p, ctypes.POINTER(_via.IrmVia)],
+    ),
+    "irm_eval_cost_grad_via": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_float, ctypes.c_float, ctypes.c_float, c_float_p, c_float_p, c_float_p, c_float_p,
+         ctypes.POINTER(_via.IrmVia)],
+    ),
+    "irm_constraints_via": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, c_uint8_p, c_float_p, c_float_p,
+         ctypes.POINTER(_via.IrmVia), c_float_p],
+    ),
+    "irm_optimize_batch_via": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, c_float_p, c_float_p, ctypes.POINTER(IrmStats), c_float_p, c_float_p, c_float_p,
+         ctypes.POINTER(_via.IrmVia)],
+    ),
+    "irm_optimize_batch_via_dev": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.POINTER(IrmBatchDev), c_float_p, c_float_p, ctypes.c_void_p, ctypes.POINTER(_via.IrmVia)],
+    ),
+    "irm_optimize_plan_via": (
+        ctypes.c_int,
+        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(IrmLaunchPlan),
+         ctypes.POINTER(_via.IrmVia)],
     ),
     "irm_build_id": (ctypes.c_char_p, []),
     "irm_debug_phase_profile": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),

@@ -5,6 +5,7 @@ import numpy as np
 
 from .environment import Environment
 from .trajectory import Trajectory
+from .via import via_from_args
 
 
 class _PersistentOptimizer:
@@ -49,6 +50,12 @@ class _PersistentOptimizer:
         if getattr(args, "goal_xy", None) is not None:
             self.goal_xy = np.asarray(args.goal_xy, np.float32)
             self.env.goal_config = self.context.ik_seed(self.env.start_config, self.goal_xy)[0]
+        # --via-joint / --via-xy: interior support rows held to joint or end-effector targets, the same for every
+        # problem of a batch (None: no via-point — the calls below are then the existing ones)
+        self.via = via_from_args(args, self.context.N, self.context.D)
+        if self.via is not None:
+            print("via-points at support rows", self.via.rows, "of", self.context.N,
+                  "(times", [float(t) for t in np.round(np.asarray(self.via.rows) / (self.context.N - 1), 4)], ")")
         self.last_stats = None
         self.last_profile = {}
         t1 = time.time()
@@ -61,7 +68,7 @@ class _PersistentOptimizer:
         t0 = time.perf_counter()
         res = self.context.optimize(self.env.start_config, self.env.goal_config, self.env.obstacles,
                                     series=self.extendedVis, obstacle_velocity=self.obstacle_velocity,
-                                    goal_xy=self.goal_xy)
+                                    goal_xy=self.goal_xy, via=self.via)
         self.last_profile = {"optimize_ms": 1000 * (time.perf_counter() - t0)}
         if self.extendedVis:
             alpha, traj, stats, series = res
@@ -84,11 +91,13 @@ class _PersistentOptimizer:
         D = self.trajectory.robot.N_joints
         start = np.asarray(start, np.float32).reshape(-1, D)
         goal = np.asarray(goal, np.float32).reshape(-1, D)
-        a_c, _, st_c = coarse.optimize(start, goal, obstacles, obstacle_velocity=vel, goal_xy=goal_xy)
+        # (the via-points of the coarse stage: the flags' times on the coarse grid)
+        a_c, _, st_c = coarse.optimize(start, goal, obstacles, obstacle_velocity=vel, goal_xy=goal_xy,
+                                       via=via_from_args(self.args, coarse.N, coarse.D))
         self.context.set_transfer(coarse.N, rbf_variance_src=coarse.params.rbf_variance)
         alpha0 = self.context.transfer_alpha(a_c)
         res = self.context.optimize(start, goal, obstacles, alpha0=alpha0, series=series, obstacle_velocity=vel,
-                                    goal_xy=goal_xy)
+                                    goal_xy=goal_xy, via=self.via)
         self.last_stats = res[2]
         self.last_stages = {"coarse": {"n_timesteps": coarse.N, "alpha": a_c, "stats": st_c},
                             "fine": {"n_timesteps": self.context.N, "alpha0": alpha0, "stats": res[2]}}
@@ -105,7 +114,7 @@ class _PersistentOptimizer:
         start = np.asarray(start, np.float32).reshape(-1, self.trajectory.robot.N_joints)
         goal = np.asarray(goal, np.float32).reshape(-1, self.trajectory.robot.N_joints)
         res = self.context.optimize(start, goal, obstacles, alpha0=alpha0, obstacle_stride=obstacle_stride,
-                                    series=series, obstacle_velocity=vel, goal_xy=goal_xy)
+                                    series=series, obstacle_velocity=vel, goal_xy=goal_xy, via=self.via)
         self.last_stats = res[2]
         return res
 

@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import IrmBatchDev, IrmDenseReport, IrmInfo, IrmLaunchPlan, IrmParams, IrmStats, check, load_library
+from .via import IrmVia, ViaPoints
 
 _fp = _abi.c_float_p
 
@@ -111,16 +112,30 @@ class Context:
         d["build_id"] = d["build_id"].decode()
         return d
 
-    def launch_plan(self, batch, n_obstacles=0, series=False, obstacle_velocity=None, goal_xy=None):
+    def launch_plan(self, batch, n_obstacles=0, series=False, obstacle_velocity=None, goal_xy=None, via=None):
         """The optimiser launch optimize() runs for `batch` problems (irm_optimize_plan: filled in by
         the library's own launch dispatch, nothing launched).  obstacle_velocity not None: the launch of
         a moving call (irm_optimize_plan_moving; only whether it is given matters).  goal_xy not None: the
-        launch of an end-effector-goal call (irm_optimize_plan_task; the same general kernel)."""
+        launch of an end-effector-goal call (irm_optimize_plan_task; the same general kernel).  via (a
+        ViaPoints; only its rows and kinds matter): the launch of a via call (irm_optimize_plan_via; the same
+        general kernel); None or an empty one: the launch without via-points.  The via plan, like the
+        end-effector-goal plan, is described with static obstacles: with obstacle_velocity as well the real launch
+        runs the same kernel with a second obstacle table in LDS (a larger lds_bytes, possibly a smaller
+        traj_per_block)."""
         pl = IrmLaunchPlan()
         fn = self.lib.irm_optimize_plan if obstacle_velocity is None else self.lib.irm_optimize_plan_moving
         if goal_xy is not None:
             fn = self.lib.irm_optimize_plan_task
-        check(fn(self._h, int(batch), int(n_obstacles), int(bool(series)), ctypes.byref(pl)))
+        if via is not None and len(via):
+            via.check_rows(self.N)
+            v = IrmVia()
+            v.n_via = len(via)
+            for i, (r, c) in enumerate(zip(via.rows, via.cartesian)):
+                v.row[i], v.cartesian[i] = r, c
+            check(self.lib.irm_optimize_plan_via(self._h, int(batch), int(n_obstacles), int(bool(series)),
+                                                 ctypes.byref(pl), ctypes.byref(v)))
+        else:
+            check(fn(self._h, int(batch), int(n_obstacles), int(bool(series)), ctypes.byref(pl)))
         d = {name: getattr(pl, name) for name, _ in IrmLaunchPlan._fields_}
         d["kernel"] = d["kernel"].decode()
         return d
@@ -305,6 +320,52 @@ class Context:
         """The end-effector targets of a task call: fp32 B×2 (one target broadcasts over the batch)."""
         return _f32(np.broadcast_to(_f32(goal_xy), (B, 2)))
 
+    def _via(self, via, B):
+        """The irm_via of a call (and the target array it points into, to be kept alive for the call): None for
+        via=None or an empty ViaPoints — the existing call."""
+        if via is None or len(via) == 0:
+            return None, None
+        if not isinstance(via, ViaPoints):
+            raise TypeError(f"via must be a ViaPoints, got {type(via).__name__}")
+        tg = via.padded(B, self.D)
+        v = IrmVia()
+        v.n_via = len(via)
+        for i, (r, c) in enumerate(zip(via.rows, via.cartesian)):
+            v.row[i], v.cartesian[i] = r, c
+        v.target = tg.ctypes.data
+        return v, tg
+
+    def via_seed(self, start, goal, via, goal_xy=None):
+        """α0 ((B×)N×D) through the via-points: the knot configurations start, each via-point in row order and
+        the goal — a Cartesian via-point through ik_seed started at the previous knot's configuration, the goal
+        likewise when goal_xy is given (`goal` is then not read and may be None) — interpolated linearly between
+        the knots on the support times, then fit_alpha of that path."""
+        s, single = self._batch(start, (self.D,))
+        B = s.shape[0]
+        if via is None:
+            via = ViaPoints.empty()
+        via.check_rows(self.N)
+        tg = via.padded(B, self.D)
+        knots, rows = [s], [0]
+        for i, (r, c) in enumerate(zip(via.rows, via.cartesian)):
+            if c:
+                q, _ = self.ik_seed(knots[-1], np.ascontiguousarray(tg[:, i, :2]))
+            else:
+                q = tg[:, i, :]
+            knots.append(_f32(q).reshape(B, self.D))
+            rows.append(r)
+        if goal_xy is not None:
+            q, _ = self.ik_seed(knots[-1], self._goal_xy(goal_xy, B))
+            knots.append(_f32(q).reshape(B, self.D))
+        else:
+            if goal is None:
+                raise ValueError("via_seed() needs a goal configuration or a goal_xy")
+            knots.append(_f32(np.broadcast_to(_f32(goal), (B, self.D))))
+        rows.append(self.N - 1)
+        path = via_path(self.kernel_matrices()[0], rows, knots)
+        alpha = self.fit_alpha(path)
+        return alpha[0] if single else alpha
+
     def ik_seed(self, start, goal_xy):
         """A joint configuration whose end effector is at goal_xy ((B×)2), by damped least squares started at
         `start` ((B×)D) (irm_ik_seed).  Returns (q, residual): residual = ‖f(q) − p‖; best effort — a target
@@ -322,15 +383,24 @@ class Context:
         check(self.lib.irm_ik_seed(self._h, _ptr(s), _ptr(p), B, _ptr(q), _ptr(res)))
         return (q[0], res[0]) if single else (q, res)
 
-    def eval_cost(self, alpha, obstacles, start, goal, lsg, ljl, lmax, obstacle_velocity=None, goal_xy=None):
+    def eval_cost(self, alpha, obstacles, start, goal, lsg, ljl, lmax, obstacle_velocity=None, goal_xy=None,
+                  via=None):
         """obstacle_velocity (O×2): waypoint n sees obstacle o at p + t[n]·w (irm_eval_cost_moving).
-        goal_xy ((B×)2): row N−1 is held to that end-effector target instead of `goal` (irm_eval_cost_task)."""
+        goal_xy ((B×)2): row N−1 is held to that end-effector target instead of `goal` (irm_eval_cost_task).
+        via (ViaPoints): the via terms λsg·½·Σ_v r_v² join the loss (irm_eval_cost_via)."""
         a, single = self._batch(alpha, (self.N, self.D))
         B = a.shape[0]
         s, g = self._sg(start, goal, B)
         obs = _f32(obstacles).reshape(-1, 2)
         out = np.zeros(B, np.float32)
-        if goal_xy is not None:
+        vs, vt = self._via(via, B)
+        if vs is not None:
+            vel = None if obstacle_velocity is None else self._velocity(_f32(obstacle_velocity).reshape(-1, 2), obs)
+            gxy = None if goal_xy is None else self._goal_xy(goal_xy, B)
+            check(self.lib.irm_eval_cost_via(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
+                                             float(lsg), float(ljl), float(lmax), _ptr(out), _ptr(vel), _ptr(gxy),
+                                             ctypes.byref(vs)))
+        elif goal_xy is not None:
             vel = None if obstacle_velocity is None else self._velocity(_f32(obstacle_velocity).reshape(-1, 2), obs)
             check(self.lib.irm_eval_cost_task(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
                                               float(lsg), float(ljl), float(lmax), _ptr(out), _ptr(vel),
@@ -345,14 +415,21 @@ class Context:
         return out[0] if single else out
 
     def eval_cost_grad(self, alpha, obstacles, start, goal, lsg, ljl, lmax, with_cost=False, obstacle_velocity=None,
-                       goal_xy=None):
+                       goal_xy=None, via=None):
         a, single = self._batch(alpha, (self.N, self.D))
         B = a.shape[0]
         s, g = self._sg(start, goal, B)
         obs = _f32(obstacles).reshape(-1, 2)
         grad = np.zeros_like(a)
         cost = np.zeros(B, np.float32)
-        if goal_xy is not None:
+        vs, vt = self._via(via, B)
+        if vs is not None:
+            vel = None if obstacle_velocity is None else self._velocity(_f32(obstacle_velocity).reshape(-1, 2), obs)
+            gxy = None if goal_xy is None else self._goal_xy(goal_xy, B)
+            check(self.lib.irm_eval_cost_grad_via(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
+                                                  float(lsg), float(ljl), float(lmax), _ptr(grad), _ptr(cost),
+                                                  _ptr(vel), _ptr(gxy), ctypes.byref(vs)))
+        elif goal_xy is not None:
             vel = None if obstacle_velocity is None else self._velocity(_f32(obstacle_velocity).reshape(-1, 2), obs)
             check(self.lib.irm_eval_cost_grad_task(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
                                                    float(lsg), float(ljl), float(lmax), _ptr(grad), _ptr(cost),
@@ -369,14 +446,25 @@ class Context:
             grad, cost = grad[0], cost[0]
         return (grad, cost) if with_cost else grad
 
-    def constraints(self, alpha, start, goal, goal_xy=None):
+    def constraints(self, alpha, start, goal, goal_xy=None, via=None):
         """goal_xy ((B×)2): the goal-position check is ‖f(τ_{N−1}) − p‖ < eps_position and report[1] that
-        Cartesian distance (irm_constraints_task)."""
+        Cartesian distance (irm_constraints_task).  via (ViaPoints, also an empty one): ok includes every via
+        distance < eps_position, and the via distances ((B×)V) are returned as a third value
+        (irm_constraints_via); the 11-float report is unchanged."""
         a, single = self._batch(alpha, (self.N, self.D))
         B = a.shape[0]
         s, g = self._sg(start, goal, B)
         ok = np.zeros(B, np.uint8)
         rep = np.zeros((B, 11), np.float32)
+        vs, vt = self._via(via, B)
+        if vs is not None:
+            dist = np.zeros((B, len(via)), np.float32)
+            gxy = None if goal_xy is None else self._goal_xy(goal_xy, B)
+            check(self.lib.irm_constraints_via(self._h, _ptr(a), _ptr(s), _ptr(g), B, ok.ctypes.data_as(_abi.c_uint8_p),
+                                               _ptr(rep), _ptr(gxy), ctypes.byref(vs), _ptr(dist)))
+            if single:
+                return bool(ok[0]), rep[0], dist[0]
+            return ok.astype(bool), rep, dist
         if goal_xy is None:
             check(self.lib.irm_constraints(self._h, _ptr(a), _ptr(s), _ptr(g), B,
                                            ok.ctypes.data_as(_abi.c_uint8_p), _ptr(rep)))
@@ -384,6 +472,9 @@ class Context:
             check(self.lib.irm_constraints_task(self._h, _ptr(a), _ptr(s), _ptr(g), B,
                                                 ok.ctypes.data_as(_abi.c_uint8_p), _ptr(rep),
                                                 _ptr(self._goal_xy(goal_xy, B))))
+        if via is not None:  # an empty ViaPoints: the existing call, and no distances
+            dist = np.zeros((B, 0), np.float32)
+            return (bool(ok[0]), rep[0], dist[0]) if single else (ok.astype(bool), rep, dist)
         if single:
             return bool(ok[0]), rep[0]
         return ok.astype(bool), rep
@@ -420,15 +511,23 @@ class Context:
         return (cv, cg) if with_grad else cv
 
     def optimize(self, start, goal, obstacles, alpha0=None, obstacle_stride=0, series=False, obstacle_velocity=None,
-                 goal_xy=None):
+                 goal_xy=None, via=None):
         """Batched Optimizer.optimize(): returns (alpha, traj, stats[, series]).
         obstacle_velocity (the shape of obstacles): the optimiser minimises the cost in which waypoint n
         sees obstacle o at p + t[n]·w (irm_optimize_batch_moving).
         goal_xy ((B×)2): the end effector of row N−1 is held to that target instead of the joint configuration
         `goal` (irm_optimize_batch_task); `goal` then feeds only the straight-line initialisation, and
-        goal=None means "seed it with ik_seed(start, goal_xy)"."""
+        goal=None means "seed it with ik_seed(start, goal_xy)".
+        via (ViaPoints): interior support rows held to joint or end-effector targets (irm_optimize_batch_via);
+        without alpha0 the plan starts from via_seed(start, goal, via, goal_xy).  None (or an empty one) keeps
+        the call and its initialisation as they are."""
         s, single = self._batch(start, (self.D,))
         B = s.shape[0]
+        vs, vt = self._via(via, B)
+        if vs is not None:
+            via.check_rows(self.N)
+            if alpha0 is None:
+                alpha0 = self.via_seed(s, goal, via, goal_xy=goal_xy)
         gxy = None
         if goal_xy is not None:
             gxy = self._goal_xy(goal_xy, B)
@@ -457,7 +556,12 @@ class Context:
         stats = (IrmStats * B)()
         cap = self.series_capacity() if series else 0
         ser = np.zeros((B, cap, self.N, self.D), np.float32) if series else None
-        if gxy is not None:
+        if vs is not None:
+            vel = None if obstacle_velocity is None else self._velocity(obstacle_velocity, obs)
+            check(self.lib.irm_optimize_batch_via(self._h, _ptr(a0), _ptr(s), _ptr(g), _ptr(obs), O,
+                                                  int(obstacle_stride), B, _ptr(alpha), _ptr(traj), stats, _ptr(ser),
+                                                  _ptr(vel), _ptr(gxy), ctypes.byref(vs)))
+        elif gxy is not None:
             vel = None if obstacle_velocity is None else self._velocity(obstacle_velocity, obs)
             check(self.lib.irm_optimize_batch_task(self._h, _ptr(a0), _ptr(s), _ptr(g), _ptr(obs), O,
                                                    int(obstacle_stride), B, _ptr(alpha), _ptr(traj), stats, _ptr(ser),
@@ -495,13 +599,25 @@ class Context:
             check(n)
         return out[: min(int(n_trials), n)]
 
-    def optimize_dev(self, batch_dev, stream=0, obstacle_velocity_dev=0, goal_xy_dev=0):
+    def optimize_dev(self, batch_dev, stream=0, obstacle_velocity_dev=0, goal_xy_dev=0, via=None, via_target_dev=0):
         """Enqueue irm_optimize_batch_dev with device pointers (IrmBatchDev).  obstacle_velocity_dev: the
         device address of the velocity table (the batch's n_obstacles / obstacle_stride), or the
         `obstacle_velocity` that batch_dev() was given; 0: the static launch.  goal_xy_dev: the device address
-        of the end-effector targets (batch × 2, irm_optimize_batch_task_dev); 0: the joint goal."""
+        of the end-effector targets (batch × 2, irm_optimize_batch_task_dev); 0: the joint goal.  via (ViaPoints;
+        its rows and kinds) with via_target_dev, the device address of the targets (batch × V × D fp32):
+        irm_optimize_batch_via_dev."""
         vel = obstacle_velocity_dev or getattr(batch_dev, "obstacle_velocity", 0)
-        if goal_xy_dev:
+        if via is not None and len(via):
+            via.check_rows(self.N)
+            v = IrmVia()
+            v.n_via = len(via)
+            for i, (r, c) in enumerate(zip(via.rows, via.cartesian)):
+                v.row[i], v.cartesian[i] = r, c
+            v.target = int(via_target_dev) if via_target_dev else None
+            check(self.lib.irm_optimize_batch_via_dev(self._h, ctypes.byref(batch_dev), _dev(vel) if vel else None,
+                                                      _dev(goal_xy_dev) if goal_xy_dev else None,
+                                                      ctypes.c_void_p(stream), ctypes.byref(v)))
+        elif goal_xy_dev:
             check(self.lib.irm_optimize_batch_task_dev(self._h, ctypes.byref(batch_dev), _dev(vel) if vel else None,
                                                        _dev(goal_xy_dev), ctypes.c_void_p(stream)))
         elif not vel:
@@ -509,6 +625,19 @@ class Context:
         else:
             check(self.lib.irm_optimize_batch_moving_dev(self._h, ctypes.byref(batch_dev), _dev(vel),
                                                          ctypes.c_void_p(stream)))
+
+
+def via_path(t, rows, knots):
+    """The piecewise-linear joint path of via_seed: B×N×D fp32 through the knot configurations `knots` (each B×D)
+    at the support rows `rows` (0 first, N−1 last), linear in the support times t between them — fp32,
+    q = a + w·(b − a) with w = (t[n] − t[r0]) / (t[r1] − t[r0])."""
+    t = np.asarray(t, np.float32)
+    B, D = knots[0].shape
+    path = np.zeros((B, t.shape[0], D), np.float32)
+    for (r0, a), (r1, b) in zip(zip(rows, knots), zip(rows[1:], knots[1:])):
+        w = ((t[r0:r1 + 1] - t[r0]) / (t[r1] - t[r0])).astype(np.float32)
+        path[:, r0:r1 + 1, :] = a[:, None, :] + w[None, :, None] * (b - a)[:, None, :]
+    return path
 
 
 def batch_dev(alpha0=0, start=0, goal=0, obstacles=0, n_obstacles=0, obstacle_stride=0, batch=0, alpha_out=0,

@@ -400,13 +400,68 @@ int check_goal_xy(const char* fn, const float* gxy, size_t B) {
     return 0;
 }
 
+// The via table of a call: V, rows, kinds and the target pointer (include/irm.h).  via = NULL or n_via = 0 is
+// no via-point (returns 0 with *V = 0).  host: the targets are host memory — every entry that is read is finite.
+int check_via(const char* fn, const irm_ctx* c, const irm_via* via, size_t B, bool host, bool need_target, int* V) {
+    *V = 0;
+    if (!via || via->n_via == 0) return 0;
+    const int N = c->N, D = c->D, nv = via->n_via;
+    if (nv < 0 || nv > IRM_MAX_VIA) return fail(IRM_EINVAL, "%s: n_via=%d outside [0, %d]", fn, nv, IRM_MAX_VIA);
+    for (int v = 0; v < nv; ++v) {
+        if (via->row[v] < 1 || via->row[v] > N - 2)
+            return fail(IRM_EINVAL, "%s: via row[%d]=%d outside [1, N-2=%d]", fn, v, via->row[v], N - 2);
+        if (v && via->row[v] <= via->row[v - 1])
+            return fail(IRM_EINVAL, "%s: via rows must be strictly increasing (row[%d]=%d after %d)", fn, v, via->row[v],
+                        via->row[v - 1]);
+        if (via->cartesian[v] != 0 && via->cartesian[v] != 1)
+            return fail(IRM_EINVAL, "%s: via cartesian[%d]=%d (0 joint target, 1 end-effector target)", fn, v,
+                        via->cartesian[v]);
+        if (via->cartesian[v] && D < 2)
+            return fail(IRM_EINVAL, "%s: an end-effector via-point needs D >= 2 (D=%d)", fn, D);
+    }
+    if (need_target && !via->target) return fail(IRM_EINVAL, "%s: via target is NULL with n_via=%d", fn, nv);
+    if (host && via->target) {
+        for (size_t b = 0; b < B; ++b)
+            for (int v = 0; v < nv; ++v) {
+                const int used = via->cartesian[v] ? 2 : D;
+                for (int d = 0; d < used; ++d)
+                    if (!std::isfinite(via->target[(b * nv + v) * D + d]))
+                        return fail(IRM_EINVAL, "%s: via target[%zu][%d][%d] is not finite", fn, b, v, d);
+            }
+    }
+    *V = nv;
+    return 0;
+}
+
+// the via table into a launch's parameters; target_dev: the targets on the device (B×V×D)
+void set_via(KParams& kp, const irm_via* via, int V, const float* target_dev) {
+    if (V <= 0) return;
+    kp.via = 1;
+    kp.n_via = V;
+    for (int v = 0; v < V; ++v) {
+        kp.via_row[v] = via->row[v];
+        kp.via_cart[v] = via->cartesian[v];
+    }
+    kp.via_target = target_dev;
+}
+
+// a via launch for which choose_shape found no trajectories-per-workgroup
+int fail_via_lds(const char* fn, const irm_ctx* c) {
+    return fail(IRM_EINVAL, "%s: no workgroup shape fits the 160 KiB LDS for N=%d with the via words", fn, c->N);
+}
+
 // Run one forward-family kernel on B host trajectories.  vel (nullable): the obstacles' velocities (O×2);
-// gxy (nullable): the end-effector targets (B×2) of an end-effector-goal call.
+// gxy (nullable): the end-effector targets (B×2) of an end-effector-goal call; via (nullable): the via-points,
+// vdist (nullable, mode 3): their distances (B×V).
 int run_forward(irm_ctx* c, int mode, const float* alpha, const float* start, const float* goal, const float* obs,
                 int O, int B, float lsg, float ljl, float lmax, int which, float* out0, float* out1, uint8_t* ok,
-                const float* vel = nullptr, const float* gxy = nullptr) {
+                const float* vel = nullptr, const float* gxy = nullptr, const irm_via* via = nullptr,
+                float* vdist = nullptr) {
     if (set_device(c)) return IRM_EDEVICE;
     if (B < 0 || !alpha) return fail(IRM_EINVAL, "bad batch arguments");
+    int V = 0;
+    if (check_via("irm_eval_cost(_grad)_via / irm_constraints_via", c, via, (size_t)std::max(B, 0), true, B > 0, &V))
+        return IRM_EINVAL;
     if (check_obs(O)) return IRM_EINVAL;
     if (!obs || O == 0) vel = nullptr;  // no obstacle, nothing moves
     if (vel && check_vel("irm_eval_cost(_grad)_moving", vel, (size_t)O * 2)) return IRM_EINVAL;
@@ -418,7 +473,7 @@ int run_forward(irm_ctx* c, int mode, const float* alpha, const float* start, co
     const size_t o_alpha = st.take(nd * 4), o_s = st.take((size_t)B * D * 4), o_g = st.take((size_t)B * D * 4),
                  o_obs = st.take((size_t)std::max(O, 1) * 8), o_out0 = st.take(std::max(nd, (size_t)B * 11) * 4),
                  o_out1 = st.take(nd * 4), o_ok = st.take((size_t)B), o_vel = st.take((size_t)std::max(O, 1) * 8),
-                 o_gxy = st.take((size_t)B * 8);
+                 o_gxy = st.take((size_t)B * 8), o_via = st.take((size_t)B * std::max(V, 1) * D * 4);
     if (ensure_io(c, st.off)) return IRM_ENOMEM;
     char* d = st.base();
     hipStream_t s = c->stream;
@@ -442,6 +497,10 @@ int run_forward(irm_ctx* c, int mode, const float* alpha, const float* start, co
         kp.task = 1;
         kp.goal_xy = (const float*)(d + o_gxy);
     }
+    if (V > 0) {
+        HIP_TRY(hipMemcpyAsync(d + o_via, via->target, (size_t)B * V * D * 4, hipMemcpyHostToDevice, s));
+        set_via(kp, via, V, (const float*)(d + o_via));
+    }
     kp.alpha0 = (const float*)(d + o_alpha);
     kp.start = (const float*)(d + o_s);
     kp.goal = (const float*)(d + o_g);
@@ -455,13 +514,16 @@ int run_forward(irm_ctx* c, int mode, const float* alpha, const float* start, co
     kp.out1 = (float*)(d + o_out1);
     kp.out_ok = (uint8_t*)(d + o_ok);
     if (choose_shape(c, B, false, kp, nullptr) <= 0)
-        return vel ? fail_moving_lds("irm_eval_cost(_grad)_moving", c, O, 0) : fail(IRM_EINVAL, "no workgroup shape fits LDS");
+        return vel ? fail_moving_lds("irm_eval_cost(_grad)_moving", c, O, 0)
+                   : V > 0 ? fail_via_lds("irm_eval_cost(_grad)_via", c) : fail(IRM_EINVAL, "no workgroup shape fits LDS");
     HIP_TRY(irm::launch_forward(kp, mode, s));
     if (out0) {
         size_t bytes = (mode == 0) ? nd * 4 : (mode == 3 ? (size_t)B * 11 * 4 : (size_t)B * 4);
         HIP_TRY(hipMemcpyAsync(out0, d + o_out0, bytes, hipMemcpyDeviceToHost, s));
     }
     if (out1) HIP_TRY(hipMemcpyAsync(out1, d + o_out1, nd * 4, hipMemcpyDeviceToHost, s));
+    // (mode 3 of a via call: the kernel wrote the via distances through out1, B×V ≤ B×N×D words)
+    if (vdist && V > 0) HIP_TRY(hipMemcpyAsync(vdist, d + o_out1, (size_t)B * V * 4, hipMemcpyDeviceToHost, s));
     if (ok) HIP_TRY(hipMemcpyAsync(ok, d + o_ok, (size_t)B, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return IRM_OK;
@@ -530,6 +592,31 @@ int irm_constraints_task(irm_ctx* c, const float* alpha, const float* start, con
     if (!c || !ok_out || !start || !goal) return fail(IRM_EINVAL, "irm_constraints_task: null argument");
     return run_forward(c, 3, alpha, start, goal, nullptr, 0, B, 0.f, 0.f, 0.f, 0, report_out, nullptr, ok_out, nullptr,
                        goal_xy);
+}
+
+int irm_eval_cost_via(irm_ctx* c, const float* alpha, const float* start, const float* goal, const float* obstacles,
+                      int32_t O, int32_t B, float lsg, float ljl, float lmax, float* cost_out,
+                      const float* obstacle_velocity, const float* goal_xy, const irm_via* via) {
+    if (!c || !cost_out || !start || !goal) return fail(IRM_EINVAL, "irm_eval_cost_via: null argument");
+    return run_forward(c, 1, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, nullptr, nullptr,
+                       obstacle_velocity, goal_xy, via);
+}
+
+int irm_eval_cost_grad_via(irm_ctx* c, const float* alpha, const float* start, const float* goal,
+                           const float* obstacles, int32_t O, int32_t B, float lsg, float ljl, float lmax,
+                           float* grad_out, float* cost_out, const float* obstacle_velocity, const float* goal_xy,
+                           const irm_via* via) {
+    if (!c || !grad_out || !start || !goal) return fail(IRM_EINVAL, "irm_eval_cost_grad_via: null argument");
+    return run_forward(c, 2, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, grad_out, nullptr,
+                       obstacle_velocity, goal_xy, via);
+}
+
+int irm_constraints_via(irm_ctx* c, const float* alpha, const float* start, const float* goal, int32_t B,
+                        uint8_t* ok_out, float* report_out, const float* goal_xy, const irm_via* via,
+                        float* via_dist_out) {
+    if (!c || !ok_out || !start || !goal) return fail(IRM_EINVAL, "irm_constraints_via: null argument");
+    return run_forward(c, 3, alpha, start, goal, nullptr, 0, B, 0.f, 0.f, 0.f, 0, report_out, nullptr, ok_out, nullptr,
+                       goal_xy, via, via_dist_out);
 }
 
 int irm_ik_seed_dev(irm_ctx* c, const float* start_dev, const float* goal_xy_dev, int32_t B, float* q_dev,
@@ -665,9 +752,13 @@ namespace {
 
 // irm_optimize_batch_dev / irm_optimize_batch_moving_dev / irm_optimize_batch_task_dev (vel, gxy: device
 // pointers, NULL for static obstacles / the joint goal)
-int optimize_dev(irm_ctx* c, const irm_batch_dev* a, const float* vel, void* stream, const float* gxy = nullptr) {
+// via (nullable): the via-points, its target a device pointer
+int optimize_dev(irm_ctx* c, const irm_batch_dev* a, const float* vel, void* stream, const float* gxy = nullptr,
+                 const irm_via* via = nullptr) {
     if (!c || !a) return fail(IRM_EINVAL, "irm_optimize_batch_dev: null argument");
     if (a->batch < 0 || !a->start || !a->goal) return fail(IRM_EINVAL, "bad batch arguments");
+    int V = 0;
+    if (check_via("irm_optimize_batch_via", c, via, (size_t)a->batch, false, a->batch > 0, &V)) return IRM_EINVAL;
     if (check_obs(a->n_obstacles) || check_stride(a->n_obstacles, a->obstacle_stride)) return IRM_EINVAL;
     if (a->n_obstacles > 0 && !a->obstacles) return fail(IRM_EINVAL, "obstacles pointer missing");
     if (set_device(c)) return IRM_EDEVICE;
@@ -694,8 +785,10 @@ int optimize_dev(irm_ctx* c, const irm_batch_dev* a, const float* vel, void* str
         kp.task = 1;
         kp.goal_xy = gxy;
     }
+    if (V > 0) set_via(kp, via, V, via->target);
     if (choose_shape(c, a->batch, true, kp, nullptr) <= 0)
         return kp.moving ? fail_moving_lds("irm_optimize_batch_moving", c, a->n_obstacles, a->obstacle_stride)
+               : V > 0   ? fail_via_lds("irm_optimize_batch_via", c)
                          : fail(IRM_EINVAL, "no workgroup shape fits LDS");
 #if defined(IRM_PHASE_PROFILE) || defined(IRM_DIV_CHECK)
     {  // (IRM_DIV_CHECK: per-block counters of the BLS division check, zeroed per launch)
@@ -718,9 +811,11 @@ int optimize_dev(irm_ctx* c, const irm_batch_dev* a, const float* vel, void* str
 }
 
 int optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series, bool moving,
-                  irm_launch_plan* out, bool task = false) {
+                  irm_launch_plan* out, bool task = false, const irm_via* via = nullptr) {
     if (!c || !out || batch <= 0) return fail(IRM_EINVAL, "irm_optimize_plan: bad argument");
     if (check_obs(n_obstacles)) return IRM_EINVAL;
+    int V = 0;
+    if (check_via("irm_optimize_plan_via", c, via, (size_t)batch, false, false, &V)) return IRM_EINVAL;
     memset(out, 0, sizeof(*out));
     KParams kp = c->kp;
     kp.B = batch;
@@ -730,8 +825,10 @@ int optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t 
     kp.record_series = (c->kp.record_series || record_series) ? 1 : 0;
     kp.moving = (moving && n_obstacles > 0) ? 1 : 0;
     kp.task = task ? 1 : 0;
+    if (V > 0) set_via(kp, via, V, nullptr);
     if (choose_shape(c, batch, true, kp, nullptr) <= 0)
         return kp.moving ? fail_moving_lds("irm_optimize_plan_moving", c, n_obstacles, 0)
+               : V > 0   ? fail_via_lds("irm_optimize_plan_via", c)
                          : fail(IRM_EINVAL, "no workgroup shape fits LDS");
     irm::LaunchDesc d{};
     d.describe_only = true;
@@ -780,6 +877,16 @@ int irm_optimize_batch_task_dev(irm_ctx* c, const irm_batch_dev* a, const float*
 int irm_optimize_plan_task(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series,
                            irm_launch_plan* out) {
     return optimize_plan(c, batch, n_obstacles, record_series, false, out, true);
+}
+
+int irm_optimize_batch_via_dev(irm_ctx* c, const irm_batch_dev* a, const float* obstacle_velocity_dev,
+                               const float* goal_xy_dev, void* stream, const irm_via* via) {
+    return optimize_dev(c, a, obstacle_velocity_dev, stream, goal_xy_dev, via);
+}
+
+int irm_optimize_plan_via(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series,
+                          irm_launch_plan* out, const irm_via* via) {
+    return optimize_plan(c, batch, n_obstacles, record_series, false, out, true, via);
 }
 
 int irm_set_work_queue(irm_ctx* c, int32_t groups) {
@@ -1285,10 +1392,13 @@ namespace {
 
 int optimize_host(irm_ctx* c, const float* alpha0, const float* start, const float* goal, const float* obstacles,
                   int32_t O, int32_t obstacle_stride, int32_t B, float* alpha_out, float* traj_out,
-                  irm_stats* stats_out, float* series_out, const float* vel, const float* gxy = nullptr) {
+                  irm_stats* stats_out, float* series_out, const float* vel, const float* gxy = nullptr,
+                  const irm_via* via = nullptr) {
     if (!c || !start || !goal) return fail(IRM_EINVAL, "irm_optimize_batch: null argument");
     if (check_obs(O) || check_stride(O, obstacle_stride)) return IRM_EINVAL;
     if (set_device(c)) return IRM_EDEVICE;
+    int V = 0;
+    if (check_via("irm_optimize_batch_via", c, via, (size_t)std::max(B, 0), true, B > 0, &V)) return IRM_EINVAL;
     if (B <= 0) return B == 0 ? IRM_OK : fail(IRM_EINVAL, "negative batch");
     const int N = c->N, D = c->D;
     const size_t nd = (size_t)B * N * D;
@@ -1301,11 +1411,18 @@ int optimize_host(irm_ctx* c, const float* alpha0, const float* start, const flo
     const size_t o_a0 = st.take(nd * 4), o_s = st.take((size_t)B * D * 4), o_g = st.take((size_t)B * D * 4),
                  o_o = st.take(std::max<size_t>(nobs, 1) * 4), o_ao = st.take(nd * 4), o_to = st.take(nd * 4),
                  o_st = st.take((size_t)B * sizeof(irm_stats)), o_se = st.take(std::max<size_t>(nser, 1) * 4),
-                 o_w = st.take(std::max<size_t>(nobs, 1) * 4), o_p = st.take((size_t)B * 8);
+                 o_w = st.take(std::max<size_t>(nobs, 1) * 4), o_p = st.take((size_t)B * 8),
+                 o_via = st.take((size_t)B * std::max(V, 1) * D * 4);
     if (ensure_io(c, st.off)) return IRM_ENOMEM;
     char* d = st.base();
     hipStream_t s = c->stream;
     if (gxy) HIP_TRY(hipMemcpyAsync(d + o_p, gxy, (size_t)B * 8, hipMemcpyHostToDevice, s));
+    irm_via vdev{};
+    if (V > 0) {
+        HIP_TRY(hipMemcpyAsync(d + o_via, via->target, (size_t)B * V * D * 4, hipMemcpyHostToDevice, s));
+        vdev = *via;
+        vdev.target = (const float*)(d + o_via);
+    }
     if (alpha0) HIP_TRY(hipMemcpyAsync(d + o_a0, alpha0, nd * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_s, start, (size_t)B * D * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_g, goal, (size_t)B * D * 4, hipMemcpyHostToDevice, s));
@@ -1325,7 +1442,8 @@ int optimize_host(irm_ctx* c, const float* alpha0, const float* start, const flo
     a.series_out = series_out ? (float*)(d + o_se) : nullptr;
     KParams save = c->kp;
     if (series_out) c->kp.record_series = 1;
-    int rc = optimize_dev(c, &a, vel ? (const float*)(d + o_w) : nullptr, s, gxy ? (const float*)(d + o_p) : nullptr);
+    int rc = optimize_dev(c, &a, vel ? (const float*)(d + o_w) : nullptr, s, gxy ? (const float*)(d + o_p) : nullptr,
+                          V > 0 ? &vdev : nullptr);
     c->kp = save;
     if (rc) return rc;
     if (alpha_out) HIP_TRY(hipMemcpyAsync(alpha_out, d + o_ao, nd * 4, hipMemcpyDeviceToHost, s));
@@ -1361,6 +1479,14 @@ int irm_optimize_batch_task(irm_ctx* c, const float* alpha0, const float* start,
                             const float* goal_xy) {
     return optimize_host(c, alpha0, start, goal, obstacles, O, obstacle_stride, B, alpha_out, traj_out, stats_out,
                          series_out, obstacle_velocity, goal_xy);
+}
+
+int irm_optimize_batch_via(irm_ctx* c, const float* alpha0, const float* start, const float* goal,
+                           const float* obstacles, int32_t O, int32_t obstacle_stride, int32_t B, float* alpha_out,
+                           float* traj_out, irm_stats* stats_out, float* series_out, const float* obstacle_velocity,
+                           const float* goal_xy, const irm_via* via) {
+    return optimize_host(c, alpha0, start, goal, obstacles, O, obstacle_stride, B, alpha_out, traj_out, stats_out,
+                         series_out, obstacle_velocity, goal_xy, via);
 }
 
 }  // extern "C"

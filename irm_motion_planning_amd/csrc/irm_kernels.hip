@@ -198,14 +198,15 @@ hipError_t launch_optimize(const KParams& p, hipStream_t s, LaunchDesc* desc) {
     // single loop over DenseShape (the other flows, workgroup sizes: the general kernel below)
     // (a moving launch runs k_optimize<DynShape<D>>, as a whole-robot launch does: the shape-specialised
     // kernels have no moving variant, and k_optimize has no work queue; an end-effector-goal launch, p.task,
-    // likewise)
-    if (p.v_ident && p.D == 7 && p.N == 256 && p.RP == p.NK && !p.whole_robot && !p.moving && !p.task && p.lean_ok) {
+    // and a via launch, p.via, likewise)
+    if (p.v_ident && p.D == 7 && p.N == 256 && p.RP == p.NK && !p.whole_robot && !p.moving && !p.task && !p.via &&
+        p.lean_ok) {
         bool served = false;
         const hipError_t e = launch_dense_shape<DenseShape<7, 256>>(p, s, desc, &served);
         if (served) return e;
     }
     // shape-specialised kernels for the common configurations (auto rank R = 32)
-    if (p.RP == 32 && p.nsplit == stage1_splits(p.NK) && !p.whole_robot && !p.moving && !p.task) {
+    if (p.RP == 32 && p.nsplit == stage1_splits(p.NK) && !p.whole_robot && !p.moving && !p.task && !p.via) {
 #define IRM_TRY_FIX(D_, N_) \
         if (p.D == D_ && p.N == N_) return launch_optimize_shape<FixShape<D_, N_, 32>>(p, s, desc);
         IRM_FIX_SHAPES(IRM_TRY_FIX)

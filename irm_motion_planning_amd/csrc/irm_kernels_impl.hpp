@@ -249,6 +249,38 @@ __device__ __forceinline__ void task_end_row(const EE<D>& ee, float px, float py
     for (int d = 0; d < D; ++d) ge[d] = fmaf(ee.jy[d], ey, ee.jx[d] * ex);
 }
 
+// Via-points (P.via, include/irm.h): the via-point this lane's row n carries — −1 none, else v + 4·cartesian[v]
+// (rows are strictly increasing: at most one matches).  Unrolled over the table, so every read of the
+// kernel-argument arrays has a constant index.
+__device__ __forceinline__ int via_code(const KParams& P, int n) {
+    int code = -1;
+#pragma unroll
+    for (int i = 0; i < IRM_MAX_VIA; ++i)
+        if (i < P.n_via && n == P.via_row[i]) code = i + 4 * (P.via_cart[i] != 0 ? 1 : 0);
+    return code;
+}
+// The via row's terms (r², ge) of via-point `code` of problem b from the row's waypoint q and its evaluation's
+// ee, in the fp32 order include/irm.h defines.  FMA: the joint distance accumulates as the calling kernel
+// accumulates row N−1 against the joint goal — fmaf(e, e, a) in k_optimize, a += e·e in k_forward.
+template <int D, bool FMA>
+__device__ __forceinline__ void via_row_terms(const KParams& P, size_t b, int code, const float (&q)[D],
+                                              const EE<D>& ee, float (&ge)[D], float& r2) {
+    const float* c = P.via_target + (b * (size_t)P.n_via + (size_t)(code & 3)) * D;
+    if (code & 4) {
+        if constexpr (D >= 2) task_end_row<D>(ee, c[0], c[1], ge, r2);  // (D = 1: refused by the host)
+        return;
+    }
+    float a = 0.f;
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+        const float e = q[d] - c[d];
+        ge[d] = e;
+        if constexpr (FMA) a = fmaf(e, e, a);
+        else a += e * e;
+    }
+    r2 = a;
+}
+
 // robot.py:29-36 (fk), 75-87 (jacobian); environment.py:46-58
 // (compute_cost_vg); trajectory.py:215-227, 245-255 (penalty elements).
 // WHOLE: the potential is summed over every joint position p_j = fk_joint_j
@@ -547,7 +579,9 @@ template <int D>
 __device__ __forceinline__ void grad_waypoint(const KParams& P, const WP<D>& w, const float (&q)[D],
                                               const float (&v)[D], int n, int idx, float lsg, float ljl,
                                               const float (&s)[D], const float (&g)[D], float (&a)[D],
-                                              float (&b)[D], bool task_row = false) {
+                                              float (&b)[D], bool task_row = false, bool via_row = false) {
+    // via_row: this lane's row (in 1 … N−2) carries a via-point and g holds its ge (via_row_terms); the position
+    // term only — a via row's velocity is free
     const int N = P.N;
     const float wt = (n == idx ? P.lam_max : 0.f) + P.one_m_lmax * P.invN;
     const float wx = wt * w.gx, wy = wt * w.gy;
@@ -562,6 +596,7 @@ __device__ __forceinline__ void grad_waypoint(const KParams& P, const WP<D>& w, 
             sgp = task_row ? g[d] : q[d] - g[d];
             sgv = v[d];
         }
+        if (via_row) sgp = g[d];
         float jpg = 0.f, jvg = 0.f;
         const bool m = (q[d] > P.thr_hi) || (q[d] < P.thr_lo);
         if (m) jpg = ((q[d] - P.mean_pos) * P.inv_std2) * P.invN;
@@ -592,12 +627,14 @@ __device__ __forceinline__ LeanW lean_weights(const KParams& P, float ljl) {
 // masks and normalised deviations reused from the evaluation).  lsg_ep = λsg on rows 0 and N−1, else
 // 0 (per lane); tg the row's start / goal.
 // TASK (k_optimize<DynShape<D>>): on the lane with task_row — row N−1 of an end-effector-goal launch — tg
-// holds ge = J_eeᵀ·(f − p) (task_end_row), which takes the place of q − tg.
+// holds ge = J_eeᵀ·(f − p) (task_end_row), which takes the place of q − tg.  lsg_pos: the weight of the position
+// term — lsg_ep on every row but a via row (via_row_terms: task_row set, tg its ge), where it is λsg while
+// lsg_ep, which also weighs v[d], stays 0: a via row's velocity is free.
 template <int D, bool TASK = false>
 __device__ __forceinline__ void grad_waypoint_lean(const KParams& P, const WP<D>& w, const float (&q)[D],
                                                    const float (&v)[D], bool isidx, float lsg_ep,
                                                    const LeanW& c, const float (&tg)[D], float (&a)[D],
-                                                   float (&b)[D], bool task_row = false) {
+                                                   float (&b)[D], bool task_row = false, float lsg_pos = 0.f) {
     const float wt = (isidx ? P.lam_max : 0.f) + c.c_mean;
     const float wx = wt * w.gx, wy = wt * w.gy;
     float zm[D], zvm[D];
@@ -613,8 +650,12 @@ __device__ __forceinline__ void grad_waypoint_lean(const KParams& P, const WP<D>
 #pragma unroll
     for (int d = 0; d < D; ++d) {
         float sgp = q[d] - tg[d];
-        if constexpr (TASK) sgp = task_row ? tg[d] : sgp;
-        a[d] = fmaf(c.k_pos, zm[d], fmaf(lsg_ep, sgp, fmaf(wx, w.jx[d], wy * w.jy[d])));
+        float lp = lsg_ep;
+        if constexpr (TASK) {
+            sgp = task_row ? tg[d] : sgp;
+            lp = lsg_pos;
+        }
+        a[d] = fmaf(c.k_pos, zm[d], fmaf(lp, sgp, fmaf(wx, w.jx[d], wy * w.jy[d])));
         b[d] = fmaf(lsg_ep, v[d], c.k_vel * zvm[d]);
     }
 }
@@ -673,8 +714,11 @@ __device__ __forceinline__ void eval_partials(const KParams& P, bool live, const
 }
 
 // Combine the trajectory's wave partials (fixed order) into loss + stats.
+// viaw / nvia: the trajectory's via words r_v² (a via launch), which join the start/goal position sum in index
+// order after its two terms (include/irm.h).
 __device__ __forceinline__ EvalOut eval_finalize(const KParams& P, const float* red, const float* sg, int t,
-                                                 int wave0, int nwt, float lsg, float ljl) {
+                                                 int wave0, int nwt, float lsg, float ljl,
+                                                 const float* viaw = nullptr, int nvia = 0) {
     const float* r = red + wave0 * kRedW;
     float cmax = r[0];
     int cidx = __float_as_int(r[1]);
@@ -691,7 +735,8 @@ __device__ __forceinline__ EvalOut eval_finalize(const KParams& P, const float* 
     }
     const float a0 = sg[t * 4 + 0], b0 = sg[t * 4 + 1], a1 = sg[t * 4 + 2], b1 = sg[t * 4 + 3];
     const float nN = (float)P.N;
-    const float sgpc = 0.5f * a0 + 0.5f * a1;                          // trajectory.py:187
+    float sgpc = 0.5f * a0 + 0.5f * a1;                                // trajectory.py:187
+    for (int i = 0; i < nvia; ++i) sgpc = sgpc + 0.5f * viaw[t * IRM_MAX_VIA + i];
     const float sgvc = 0.5f * b0 + 0.5f * b1;                          // trajectory.py:203
     const float toc = P.lam_max * cmax + P.one_m_lmax * (csum / nN);    // trajectory.py:85-87
     EvalOut e;
@@ -1238,7 +1283,9 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
     if (OPS_LDS && !REGOPS) {
         bool mov = false;  // (only the DynShape instantiations have the moving variant)
         if constexpr (S::kVariants) mov = P.moving != 0;
-        const Plan L = plan_lds(P, OPS_LDS, true, false, mov);
+        bool vias = false;  // (nor the via words, which precede the staged operators)
+        if constexpr (S::kVariants) vias = P.via != 0;
+        const Plan L = plan_lds(P, OPS_LDS, true, false, mov, vias);
         const int n1 = (int)frag_floats(RP, MP) / 4, n2 = (int)frag_floats(MP, RP) / 4;
         const f32x4* g1 = reinterpret_cast<const f32x4*>(P.F1frag);
         const f32x4* g2 = reinterpret_cast<const f32x4*>(P.F2frag);
@@ -1363,6 +1410,21 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
     // evaluation — one lane, an L2 hit — so that nothing more stays in registers across the rounds)
     bool task_row = false;
     if constexpr (S::kVariants) task_row = P.task && valid && n == N - 1;
+    // via-points (DynShape launches only): the lane of row m_v (via_code; rows lie in 1 … N−2, so never a
+    // start / goal row) and the trajectories' via words r_v², a region of its own behind the obstacles
+    // (recomputed from the kernel arguments where they are used: nothing more lives across the rounds)
+    auto via_of = [&]() -> int {
+        if constexpr (S::kVariants) return (P.via && valid) ? via_code(P, n) : -1;
+        else return -1;
+    };
+    auto via_count = [&]() -> int {
+        if constexpr (S::kVariants) return P.via ? P.n_via : 0;
+        else return 0;
+    };
+    auto via_words = [&]() -> float* {
+        return smem + obs_region_end(P, H.obs, P.moving != 0) + t * IRM_MAX_VIA;  // Plan::via (plan_lds), this
+                                                                                  // trajectory's words
+    };
 
     // stage 1 over the units of this wave: Ypart[s] = Fᵀ·[a'; b'] (velocity half if `full`)
     auto stage1 = [&](bool full) {
@@ -1829,6 +1891,13 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
                     // end-effector goal: the end row's ge = J_eeᵀ·(f − p) replaces this lane's copy of the
                     // joint goal (not read again in such a launch) and r² the squared joint distance below
                     if (task_row) task_end_row<D>(ee, P.goal_xy[b * 2], P.goal_xy[b * 2 + 1], g, task_r2);
+                    // via row: ge_v likewise (an interior row never reads its copy of the joint goal), r_v²
+                    // to the trajectory's via words (the lane reads its target in every evaluation, as above)
+                    if (const int via = via_of(); via >= 0) {
+                        float r2 = 0.f;
+                        via_row_terms<D, true>(P, b, via, q2, ee, g, r2);
+                        via_words()[via & 3] = r2;
+                    }
                 } else {
                     eval_waypoint<D, false, true, true>(P, q2, v2, obs, w);
                 }
@@ -1869,7 +1938,16 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
             }
             const float e_a0 = sg[t * 4 + 0], e_b0 = sg[t * 4 + 1], e_a1 = sg[t * 4 + 2], e_b1 = sg[t * 4 + 3];
             IRM_STAMP(18);
-            const float sgpc = fmaf(0.5f, e_a0, 0.5f * e_a1);                   // trajectory.py:187
+            float sgpc = fmaf(0.5f, e_a0, 0.5f * e_a1);                         // trajectory.py:187
+            bool via_ok = true;  // every via distance below eps_position (read by the resync's check)
+            if constexpr (S::kVariants) {  // the via terms, in index order after the two (include/irm.h)
+                const int nvia = via_count();
+                for (int i = 0; i < nvia; ++i) {
+                    const float r2 = via_words()[i];
+                    sgpc = fmaf(0.5f, r2, sgpc);
+                    via_ok = via_ok && sqrtf(r2) < cold[C_EPSP];
+                }
+            }
             const float sgvc = fmaf(0.5f, e_b0, 0.5f * e_b1);                   // trajectory.py:203
             // trajectory.py:85-87 + 281 (mean and joint-limit terms pre-summed in usum)
             const float nl = fmaf(lsg, sgpc + sgvc, fmaf(P.lam_max, cmax, usum));
@@ -1894,8 +1972,9 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
                 // constraintsFulfilled(α) (trajectory.py:129-137, robot.py:90-113) on the
                 // materialised α; optimizer_GD.py:214-224 / optimizer_BLS.py:201-211
                 const float eps_p = cold[C_EPSP], eps_v = cold[C_EPSV];
-                const bool ok = sqrtf(e_a0) < eps_p && sqrtf(e_a1) < eps_p && sqrtf(e_b0) < eps_v &&
-                                sqrtf(e_b1) < eps_v && tx <= cold[C_PMAX] && tn >= cold[C_PMIN] && va <= cold[C_VMAX];
+                bool ok = sqrtf(e_a0) < eps_p && sqrtf(e_a1) < eps_p && sqrtf(e_b0) < eps_v &&
+                          sqrtf(e_b1) < eps_v && tx <= cold[C_PMAX] && tn >= cold[C_PMIN] && va <= cold[C_VMAX];
+                ok = ok && via_ok;
                 if (!bls || cold_int(C_MAXOUT) > 0) st.outer_iterations++;
                 st.constraints_ok = ok ? 1 : 0;
                 if (ok) {
@@ -1981,10 +2060,12 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
             if (valid) {
                 float a[D], bb[D], tg[D];
                 const bool endrow = (n == 0 || n == N - 1);
+                const bool viar = via_of() >= 0;
 #pragma unroll
-                for (int k = 0; k < D; ++k) tg[k] = (n == N - 1) ? g[k] : s[k];
+                for (int k = 0; k < D; ++k) tg[k] = (n == N - 1 || viar) ? g[k] : s[k];
+                // (a via row: g holds ge_v, weighed by λsg in a only — lsg_ep, which weighs v in b, stays 0)
                 grad_waypoint_lean<D, S::kVariants>(P, w, q2, v2, n == cidx, endrow ? lsg_e : 0.f, lean_weights(P, ljl_e),
-                                                    tg, a, bb, task_row);
+                                                    tg, a, bb, task_row || viar, (endrow || viar) ? lsg_e : 0.f);
 #pragma unroll
                 for (int k = 0; k < D; ++k) {
                     float ma = 0.f, mb = 0.f;
@@ -4487,7 +4568,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
 template <int D, int MAXT>
 __global__ __launch_bounds__(MAXT) void k_forward(KParams P, int mode) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const Plan L = plan_lds(P, false, false, false, P.moving != 0);
+    const Plan L = plan_lds(P, false, false, false, P.moving != 0, P.via != 0);
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int N = P.N, NW = P.NW, TB = P.TB, MP = P.MP;
@@ -4504,6 +4585,7 @@ __global__ __launch_bounds__(MAXT) void k_forward(KParams P, int mode) {
     float* red = smem + L.red;
     float* sg = smem + L.sg;
     float* obsL = smem + L.obs;
+    float* viaw = smem + L.via;  // (a via launch: L.via is a region of its own)
 
     stage_obstacles<true>(P, tb0, ntb, obsL);
     stage_alpha<D>(P, tb0, ntb, XG, MP);
@@ -4527,17 +4609,27 @@ __global__ __launch_bounds__(MAXT) void k_forward(KParams P, int mode) {
     WP<D> w;
     const bool task_row = P.task && valid && n == N - 1;
     float task_r2 = 0.f;
+    // via-points: the lane of row m_v (rows lie in 1 … N−2, so never a start / goal row)
+    const int via = (P.via && valid) ? via_code(P, n) : -1;
     if (tvalid) {
         // (obstacles: shared only here, obs_stride 0 — the velocity table follows the one position table)
         EE<D> ee;
         if (valid) eval_waypoint_rt<D, true>(P, q, v, obsL, w, obsL + obs_vel_offset(P), P.moving ? P.tsup[n] : 0.f, &ee);
         // end-effector goal: ge = J_eeᵀ·(f − p) replaces this lane's copy of the joint goal
         if (task_row) task_end_row<D>(ee, P.goal_xy[b * 2], P.goal_xy[b * 2 + 1], g, task_r2);
+        // via row: ge_v replaces this lane's copy of the joint goal (an interior row never reads it) and r_v²
+        // goes to the trajectory's via words
+        if (via >= 0) {
+            float r2 = 0.f;
+            via_row_terms<D, false>(P, b, via, q, ee, g, r2);
+            viaw[t * IRM_MAX_VIA + (via & 3)] = r2;
+        }
         eval_partials<D>(P, valid, w, n, wave, q, v, s, g, red, sg, t, task_row, task_r2);
     }
     __syncthreads();
     EvalOut E{};
-    if (tvalid) E = eval_finalize(P, red, sg, t, t * WPT, WPT, P.lam_sg, P.lam_jl);
+    const int nvia = P.via ? P.n_via : 0;
+    if (tvalid) E = eval_finalize(P, red, sg, t, t * WPT, WPT, P.lam_sg, P.lam_jl, viaw, nvia);
     if (tvalid && n == 0) {
         if (mode == 1 || mode == 2) {
             if (P.out0) P.out0[b] = E.loss;
@@ -4546,7 +4638,13 @@ __global__ __launch_bounds__(MAXT) void k_forward(KParams P, int mode) {
             const bool f1 = E.vs < P.eps_v && E.vg < P.eps_v;
             const bool f2 = E.tmax <= P.pmax && E.tmin >= P.pmin;
             const bool f3 = E.vabs <= P.vmax;
-            if (P.out_ok) P.out_ok[b] = (f0 && f1 && f2 && f3) ? 1 : 0;
+            bool fv = true;  // every via distance below eps_position (the 11-float report stays as it is)
+            for (int i = 0; i < nvia; ++i) {
+                const float dv = sqrtf(viaw[t * IRM_MAX_VIA + i]);
+                fv = fv && dv < P.eps_p;
+                if (P.out1) P.out1[b * nvia + i] = dv;
+            }
+            if (P.out_ok) P.out_ok[b] = (f0 && f1 && f2 && f3 && fv) ? 1 : 0;
             if (P.out0) {
                 float* r = P.out0 + b * 11;
                 r[0] = E.ds; r[1] = E.dg; r[2] = E.vs; r[3] = E.vg;
@@ -4558,7 +4656,7 @@ __global__ __launch_bounds__(MAXT) void k_forward(KParams P, int mode) {
     if (mode != 2) return;
     if (valid) {
         float a[D], bb[D];
-        grad_waypoint<D>(P, w, q, v, n, E.idx, P.lam_sg, P.lam_jl, s, g, a, bb, task_row);
+        grad_waypoint<D>(P, w, q, v, n, E.idx, P.lam_sg, P.lam_jl, s, g, a, bb, task_row, via >= 0);
 #pragma unroll
         for (int k = 0; k < D; ++k) {
             XG[n * kLd + t * D + k] = a[k];
@@ -4840,7 +4938,7 @@ hipError_t launch_dense_shape(const KParams& p, hipStream_t s, LaunchDesc* desc,
 template <class Sh>
 hipError_t launch_general_shape(const KParams& p, hipStream_t s, LaunchDesc* desc) {
     const bool stage = p.ops_in_lds != 0;
-    const Plan L = plan_lds(p, stage, true, false, Sh::kVariants && p.moving != 0);
+    const Plan L = plan_lds(p, stage, true, false, Sh::kVariants && p.moving != 0, Sh::kVariants && p.via != 0);
     const size_t lds = (size_t)L.total * 4;
     const int grid = (p.B + p.TB - 1) / p.TB;
     if (grid <= 0) return hipSuccess;
@@ -4883,7 +4981,7 @@ hipError_t launch_general_shape(const KParams& p, hipStream_t s, LaunchDesc* des
 
 template <int D>
 hipError_t launch_forward_dim(const KParams& p, int mode, hipStream_t s) {
-    const Plan L = plan_lds(p, false, false, false, p.moving != 0);
+    const Plan L = plan_lds(p, false, false, false, p.moving != 0, p.via != 0);
     const size_t lds = (size_t)L.total * 4;
     const int grid = (p.B + p.TB - 1) / p.TB;
     if (grid <= 0) return hipSuccess;

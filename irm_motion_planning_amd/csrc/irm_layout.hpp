@@ -124,6 +124,15 @@ struct KParams {
     // the moving block.  task: the launch reads goal_xy (k_forward, k_optimize<DynShape<D>>)
     int32_t task;
     const float* goal_xy;
+    // via-points (irm_*_via): support row via_row[v] is held to via_target[(b·n_via + v)·D ...] — all D values
+    // a joint configuration (via_cart[v] = 0), the first two an end-effector position (1) — in the loss, the
+    // position gradient input of that row and the constraint, include/irm.h.  Appended like the task block.
+    // via: the launch reads them (k_forward, k_optimize<DynShape<D>>) and the LDS layout holds the via words
+    // (plan_lds).  k_forward's constraints mode writes the via distances (B×n_via) through out1 when set.
+    int32_t via, n_via;
+    int32_t via_row[IRM_MAX_VIA];
+    int32_t via_cart[IRM_MAX_VIA];
+    const float* via_target;
 };
 
 constexpr int kTraceW = 10;  // outer, inner, trial, lr, new_loss, required_loss, accepted, loss, ‖g‖, alpha_norm
@@ -164,6 +173,7 @@ struct Plan {
     int red, sg, wp;             // wave partials, start/goal rows, BLS Gram partials
     int flags, act, list;        // per-trajectory flags, active sparse rows
     int obs;                     // obstacles (shared or per trajectory)
+    int via;                     // via words r_v² ([trajectory][IRM_MAX_VIA]; via launches only, else 0)
     int total;
 };
 
@@ -228,8 +238,17 @@ __host__ __device__ constexpr Head plan_head(int MP, int RP, int nsplit, bool op
 // moving: the launch stages the obstacles' velocity table behind the positions — twice the obstacle words.
 // (An argument, not a read of p.moving: the callers that can run a moving launch pass it, and the code of the
 // kernels without the variant stays as it is.)
+// via: the launch keeps each trajectory's via words r_v² in a region of its own behind the obstacles —
+// kMaxTraj·IRM_MAX_VIA floats, so that it aliases nothing at any workgroup size (`sg` sits directly behind `red`
+// in the head, whose layout the shape-specialised kernels see at compile time and which stays as it is).
+// End of the obstacle region that starts at `obs` (Head::obs): where the via words of a via launch lie and what
+// follows the obstacles otherwise — the one formula plan_lds and the optimiser kernel (which addresses the via
+// words from the head it already holds) share.
+__host__ __device__ inline int obs_region_end(const KParams& p, int obs, bool moving) {
+    return obs + al4((moving ? 2 : 1) * (p.obs_stride ? p.TB : 1) * ((p.O + 3) & ~3) * 2 + 4);
+}
 __host__ __device__ inline Plan plan_lds(const KParams& p, bool ops_lds, bool optimizer, bool lean = false,
-                                         bool moving = false) {
+                                         bool moving = false, bool via = false) {
     const Head H = plan_head(p.MP, p.RP, p.nsplit, optimizer, lean);
     Plan L{};
     L.X = H.X;
@@ -243,7 +262,12 @@ __host__ __device__ inline Plan plan_lds(const KParams& p, bool ops_lds, bool op
     L.wp = H.wp;
     L.flags = H.flags;
     L.obs = H.obs;
-    int off = H.obs + al4((moving ? 2 : 1) * (p.obs_stride ? p.TB : 1) * ((p.O + 3) & ~3) * 2 + 4);
+    int off = obs_region_end(p, H.obs, moving);
+    L.via = 0;
+    if (via) {
+        L.via = off;
+        off += kMaxTraj * IRM_MAX_VIA;
+    }
     L.f1 = L.f2 = 0;
     if (optimizer && ops_lds && !p.regops) {  // with REGOPS the A-fragments live in VGPRs
         L.f1 = off;

@@ -668,13 +668,13 @@ int choose_shape(int N, int D, int NK, int RP, int MP, int traj_per_block, int n
         }
         if (optimizer) {
             kp.regops = irm::regops_fit(kp) ? 1 : 0;
-            irm::Plan a = irm::plan_lds(kp, true, true, false, kp.moving != 0);
+            irm::Plan a = irm::plan_lds(kp, true, true, false, kp.moving != 0, kp.via != 0);
             if ((size_t)a.total * 4 <= lds_cap) {
                 kp.ops_in_lds = 1;
                 if (lds_bytes_out) *lds_bytes_out = a.total * 4;
                 return tb;
             }
-            irm::Plan b = irm::plan_lds(kp, false, true, false, kp.moving != 0);
+            irm::Plan b = irm::plan_lds(kp, false, true, false, kp.moving != 0, kp.via != 0);
             if ((size_t)b.total * 4 <= lds_cap) {
                 kp.ops_in_lds = 0;
                 kp.regops = 0;
@@ -682,7 +682,7 @@ int choose_shape(int N, int D, int NK, int RP, int MP, int traj_per_block, int n
                 return tb;
             }
         } else {
-            irm::Plan a = irm::plan_lds(kp, false, false, false, kp.moving != 0);
+            irm::Plan a = irm::plan_lds(kp, false, false, false, kp.moving != 0, kp.via != 0);
             if ((size_t)a.total * 4 <= lds_cap) {
                 if (lds_bytes_out) *lds_bytes_out = a.total * 4;
                 return tb;

@@ -10,9 +10,11 @@ Additive flags (no reference counterpart): --batch-size, --seed,
 --operator-rank, --device, --whole-robot-cost, --work-queue, --dense-check
 (which adds one stdout line and trajectory_result_dense.txt),
 --coarse-n-timesteps (coarse-to-fine: two stdout lines per optimize()),
---obstacle-velocity (obstacles that drift at a constant velocity over the plan) and
+--obstacle-velocity (obstacles that drift at a constant velocity over the plan),
 --goal-xy (an end-effector target instead of a goal configuration; the goal number of the
-"start goal position" line is then the Cartesian distance).
+"start goal position" line is then the Cartesian distance) and --via-joint / --via-xy (via-points:
+interior support rows held to joint or end-effector targets; one stdout line names the chosen rows
+and one reports the via distances).
 """
 import argparse
 import os
@@ -146,6 +148,14 @@ def build_parser():
                              "the IK seed from the start.  With --batch-size, problem 0 takes (X, Y) and every "
                              "seeded problem the end-effector position of its seeded goal configuration "
                              "(default: absent = joint goal)")
+    parser.add_argument('--via-joint', type=float, nargs='+', action='append', default=None, metavar='T_Q',
+                        help="Via-point: at plan time T (0 < T < 1, snapped to the nearest support row) the robot "
+                             "is held to the joint configuration q1 ... qD — given as T q1 ... qD; repeatable, at "
+                             "most 4 via-points with --via-xy; every problem of a batch takes them "
+                             "(default: absent)")
+    parser.add_argument('--via-xy', type=float, nargs=3, action='append', default=None, metavar=('T', 'X', 'Y'),
+                        help="Via-point: at plan time T the end effector is held to (X, Y); it passes through "
+                             "and does not stop; repeatable (default: absent)")
     return parser
 
 
@@ -283,7 +293,11 @@ def run_batch(optimizer, args):
         series = full.get("series")
     avg = tr.compute_trajectory_cost(alpha, env.obstacles, start, goal, 0, 0, 0)
     mx = tr.compute_trajectory_cost(alpha, env.obstacles, start, goal, 0, 0, 1)
-    ok, _ = optimizer.context.constraints(alpha, start, goal, goal_xy=goal_xy)
+    if optimizer.via is None:
+        ok, _ = optimizer.context.constraints(alpha, start, goal, goal_xy=goal_xy)
+    else:
+        ok, _, vdist = optimizer.context.constraints(alpha, start, goal, goal_xy=goal_xy, via=optimizer.via)
+        print("via distances: max over the batch", [float(d) for d in np.max(vdist, axis=0)])
     print("batch of", len(alpha), "problems" + (f" on {world} GPUs" if world > 1 else "") +
           ": constraint fulfiled", int(np.sum(ok)), "of", len(alpha),
           "; avg cost mean", float(np.mean(avg)), ", max cost mean", float(np.mean(mx)),
@@ -375,6 +389,11 @@ def main(argv=None):
     max_result_cost = tr.compute_trajectory_cost(result_alpha, env.obstacles, env.start_config, env.goal_config, 0, 0, 1)
     ok = tr.constraintsFulfilledVerbose(result_alpha, env.start_config, env.goal_config, verbose=True,
                                         goal_xy=optimizer.goal_xy)
+    if optimizer.via is not None:  # the via constraint joins the flag; the reference-style report stays
+        vok, _, vdist = optimizer.context.constraints(result_alpha, env.start_config, env.goal_config,
+                                                      goal_xy=optimizer.goal_xy, via=optimizer.via)
+        print("via distances:", [float(d) for d in vdist], "(eps_position", args.eps_position, ")")
+        ok = bool(ok) and bool(vok)
     print("result cost: ( avg", avg_result_cost, ", max", max_result_cost, "). constraint fulfiled", ok)
 
     np_trajectory = np.array(tr.evaluate(result_alpha, tr.km, tr.jac))

@@ -27,6 +27,11 @@ straight line of initTrajectory (optimizer_BLS.py:57-62).
   carries it — the target is a point of the world, not of the plan's time.  Without a goal configuration the
   first such plan seeds its straight line with the IK seed (irm_ik_seed_dev), on the device.
 
+* plan(..., via=ViaPoints(...)) holds interior support rows to joint or end-effector targets (via.py); the
+  targets live on the device between plans, a plan that is not warm-started begins from Context.via_seed, and
+  advance(tau) drops them — a re-timed via-point does not generally land on a support row, so the caller
+  passes fresh ones.
+
 The first call, or warm_start=False, is exactly Optimizer.optimize() for the batch.
 A warm-started call equals irm_optimize_batch with alpha0 = the previous α_out bit for
 bit (tests/test_gpu_parity.py::test_replanner_*).
@@ -74,6 +79,8 @@ class Replanner:
         self._have_obs = False    # is there a stored obstacle table (plan(obstacles=None))?
         self.goal_xy = torch.zeros((B, 2), **f32)  # end-effector targets (plan(goal_xy=…))
         self.task = False         # does the latest plan hold the end effector to goal_xy?
+        self.via = None           # the stored via-points (plan(via=…)); None: no via-point
+        self.via_target = None    # their targets on the device (B×V×D)
         self._alpha = [torch.zeros((B, N, D), **f32), torch.zeros((B, N, D), **f32)]
         self.traj = torch.zeros((B, N, D), **f32)
         self.stats = torch.zeros((B, len(STATS_FIELDS)), dtype=torch.int32, device=self.device)
@@ -87,7 +94,7 @@ class Replanner:
         dst.copy_(self.torch.from_numpy(x).reshape(dst.shape), non_blocking=False)
 
     def plan(self, obstacles=None, start=None, goal=None, warm_start=True, stream=None, obstacle_velocity=None,
-             goal_xy=None):
+             goal_xy=None, via=None):
         """Optimise the batch against `obstacles` (O×2, or B×O×2 per problem).
 
         start / goal (B×D or D) are kept from the previous call when None.  obstacles=None re-uses the
@@ -97,6 +104,10 @@ class Replanner:
         otherwise.  goal_xy (B×2 or 2): plan to these end-effector targets; a later plan() with neither
         goal nor goal_xy keeps them, one with a goal configuration alone goes back to the joint goal.  A
         first plan with goal_xy and no goal seeds the goal configuration with the IK seed from `start`.
+        via (ViaPoints, via.py): hold interior support rows to joint or end-effector targets (V×D, or B×V×D per
+        problem); a later plan() with via=None keeps them, an empty ViaPoints drops them, and advance() drops
+        them too — a re-timed via-point does not generally land on a support row, so pass fresh ones after an
+        advance.  A via plan that is not warm-started begins from Context.via_seed, as Context.optimize does.
         Returns the per-problem statistics (dict of numpy arrays, irm_stats fields); the plan
         stays on the device (alpha(), trajectory())."""
         torch = self.torch
@@ -132,6 +143,16 @@ class Replanner:
             self.task = True
         elif goal is not None:
             self.task = False
+        if via is not None:
+            if len(via) == 0:
+                self.via, self.via_target = None, None
+            else:
+                via.check_rows(self.N)
+                tg = via.padded(B, D)
+                if not via.read_entries_finite(B, D):  # (the entries that are read, as the library checks them)
+                    raise IrmError("via targets must be finite")
+                self.via = via
+                self.via_target = torch.from_numpy(tg).to(self.device)
         if self.calls == 0 and (start is None or (goal is None and gxy is None)):
             raise IrmError("the first plan() needs start and goal (or goal_xy)")
         s = stream if stream is not None else torch.cuda.current_stream(self.device)
@@ -147,12 +168,20 @@ class Replanner:
         self._have_obs = True
         warm = bool(warm_start) and self.planned
         a_in, a_out = self._alpha[self.cur], self._alpha[self.cur ^ 1]
+        if self.via is not None and not warm:  # the via seed (Context.via_seed) is this plan's α0
+            s.synchronize()
+            a0 = self.context.via_seed(self.start.cpu().numpy(), self.goal.cpu().numpy(), self.via,
+                                       goal_xy=self.goal_xy.cpu().numpy() if self.task else None)
+            a_in.copy_(torch.from_numpy(np.ascontiguousarray(a0, np.float32).reshape(a_in.shape)))
+            torch.cuda.current_stream(self.device).synchronize()
+            warm = True
         bd = batch_dev(alpha0=a_in.data_ptr() if warm else 0, start=self.start.data_ptr(),
                        goal=self.goal.data_ptr(), obstacles=self.obstacles.data_ptr(), n_obstacles=O,
                        obstacle_stride=2 * O if self.per_problem else 0, batch=B, alpha_out=a_out.data_ptr(),
                        traj_out=self.traj.data_ptr(), stats_out=self.stats.data_ptr(),
                        obstacle_velocity=self.velocity.data_ptr() if self.moving else 0)
-        self.context.optimize_dev(bd, s.cuda_stream, goal_xy_dev=self.goal_xy.data_ptr() if self.task else 0)
+        self.context.optimize_dev(bd, s.cuda_stream, goal_xy_dev=self.goal_xy.data_ptr() if self.task else 0,
+                                  via=self.via, via_target_dev=self.via_target.data_ptr() if self.via is not None else 0)
         self.cur ^= 1
         self.planned = True
         self.calls += 1
@@ -180,9 +209,13 @@ class Replanner:
             p' = fl(p + fl(tau·w)),   w' = fl(c·w)
         (advance_obstacles: the obstacles where they are at the old plan's time tau, their remaining
         motion stretched to unit time), so plan() with obstacles=None continues against the same moving
-        scene.  Both updates are enqueued on `stream` with the transfer; nothing leaves HBM."""
+        scene.  Both updates are enqueued on `stream` with the transfer; nothing leaves HBM.
+
+        Stored via-points are dropped: their rows name support times of the old plan, and a re-timed via-point
+        does not generally land on a support row of the new one — pass fresh ones to the next plan()."""
         if not self.planned:
             raise IrmError("advance() needs a plan: call plan() first")
+        self.via, self.via_target = None, None
         tau = float(tau)
         if self._tau != tau:
             self.context.set_transfer(self.N, t0=tau, t1=1.0)  # IrmError unless tau is finite and < 1
