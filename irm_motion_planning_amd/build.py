@@ -2,14 +2,17 @@
 
     python -m irm_motion_planning_amd.build [--force] [--prof] [-j N]
 
-The optimiser templates (csrc/irm_kernels_impl.hpp) are instantiated in one
-object per problem shape (csrc/irm_opt_inst.hip compiled with IRM_INST_*), so
-the objects build in parallel; the host-API kernels and dispatch
+The optimiser templates (csrc/irm_kernels_impl.hpp and the part headers it
+includes: irm_wave / irm_prof / irm_physics / irm_opt_common /
+irm_dispatch / irm_launch_decl .hpp) are
+instantiated in one object per problem shape (csrc/irm_opt_inst.hip compiled
+with IRM_INST_*), so the objects build in parallel; the host-API kernels and dispatch
 (irm_kernels.hip), the C ABI (irm_host.cpp) and the device-free operator build
 behind irm_ctx_create (irm_operator.cpp: build_operators, fill_kparams,
 choose_shape; no HIP header) are three more objects.  irm_layout.hpp is what
 host and kernels share without a HIP type (KParams, fragment and LDS layouts),
-irm_kernels.hpp adds the launchers.  The .so lands next to this file so that it travels with the repository snapshot to the
+irm_kernels.hpp adds the launchers.  Every csrc/*.hpp is a dependency of every
+object (HEADERS).  The .so lands next to this file so that it travels with the repository snapshot to the
 GPU box (it is git-ignored, not gpurun-ignored); objects stay in _obj/.
 """
 import glob
@@ -23,9 +26,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 OUT = os.path.join(HERE, "libirm_hip.so")
-HEADERS = [os.path.join(CSRC, h) for h in ("irm_kernels.hpp", "irm_kernels_impl.hpp", "irm_layout.hpp",
-                                           "irm_operator.hpp")] + \
-    [os.path.join(HERE, "..", "include", "irm.h")]
+# every header is a dependency of every object: a new header cannot be missing from the list
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.hpp"))) + [os.path.join(HERE, "..", "include", "irm.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 # -amdgpu-atomic-optimizer-strategy=None: every LDS atomic in the kernels is issued by one lane (flag
@@ -38,7 +40,7 @@ ARCH = "gfx950"
 CFLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wall", "-Wno-unused-function",
           "-ffp-contract=off", "-fno-slp-vectorize",
           "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]
-FIX_SHAPES = [(3, 50), (3, 64), (3, 128), (3, 256), (7, 128), (7, 256)]  # IRM_FIX_SHAPES in irm_kernels_impl.hpp
+FIX_SHAPES = [(3, 50), (3, 64), (3, 128), (3, 256), (7, 128), (7, 256)]  # IRM_FIX_SHAPES in irm_launch_decl.hpp
 DENSE_SHAPES = [(7, 256)]  # the dense operator's k_lean (irm_kernels.hip launch_optimize)
 QUEUE_SHAPES = [(3, 50), (3, 64), (3, 128), (7, 128)]  # the work queue's k_lean (IRM_QUEUE_SHAPES in irm_kernels_impl.hpp)
 MAX_D = 8

@@ -9,7 +9,9 @@
 // consecutive floats of a query-matrix row.  The arithmetic is eval_exact's: the exact fp32×fp32
 // products accumulate in fp64 in the order m = 0, 1, …, N−1, round once to fp32, then ·J the same way,
 // so an evaluation on the support times is irm_evaluate's to the bit.
-#include "irm_kernels_impl.hpp"
+#include "irm_dispatch.hpp"
+#include "irm_physics.hpp"  // WP, eval_waypoint_rt, stage_obstacles
+#include "irm_wave.hpp"     // wred_*, amax_step
 
 namespace irm {
 

@@ -12,7 +12,8 @@
 // order m = 0, 1, …, n_src − 1 and is rounded to fp32 once; the chains of different problems never mix, so
 // a problem's result does not depend on its batch.  Slots of the last workgroup beyond the batch stage
 // zeros and store nothing.
-#include "irm_kernels_impl.hpp"
+#include "irm_dispatch.hpp"
+#include "irm_kernels.hpp"
 
 namespace irm {
 

@@ -1,7 +1,11 @@
 // irm_kernels.hip — gfx950 host-API kernels (fk, fk_joints, compute_cost_vg,
 // initTrajectory) and the launch dispatch.  The optimiser / α-space kernels are
-// templates in irm_kernels_impl.hpp, instantiated per shape in irm_opt_inst.hip.
-#include "irm_kernels_impl.hpp"
+// templates in irm_kernels_impl.hpp, instantiated per shape in irm_opt_inst.hip; this unit
+// sees their launchers' declarations only.
+#include "irm_dispatch.hpp"
+#include "irm_launch_decl.hpp"
+#include "irm_opt_common.hpp"  // FixShape, DenseShape, DynShape
+#include "irm_physics.hpp"     // sincos_fast
 
 namespace irm {
 

@@ -1,6 +1,8 @@
 // irm_kernels_impl.hpp — gfx950 (CDNA4) kernel templates of the RKHS trajectory optimiser.
-// Included by irm_kernels.hip (host-API kernels, launch dispatch) and by the instantiation
-// units irm_opt_inst.hip (one k_optimize shape / k_forward D per object, compiled in parallel).
+// The optimiser kernels, k_forward and their launchers; included by the instantiation units
+// irm_opt_inst.hip (one k_optimize shape / k_forward D per object, compiled in parallel).
+// The helpers lie in part headers (below): irm_kernels.hip, irm_dense.hip and irm_fit.hip
+// include the parts they use and not this file.
 //
 // Hot path of simongroeger/irm_motion_planning: optimizer_GD.py:173-232 and
 // optimizer_BLS.py:126-213 over trajectory.py:271-297 / robot.py:29-87 /
@@ -30,790 +32,15 @@
 #include <type_traits>
 
 #include "irm_kernels.hpp"
+// the parts cut out so far (each includes what it needs)
+#include "irm_wave.hpp"         // packed-fp32 types, DPP wave reductions, store_tile
+#include "irm_prof.hpp"         // phase profiler, IRM_STAMP / IRM_COUNT
+#include "irm_physics.hpp"      // per-waypoint physics and its reductions
+#include "irm_opt_common.hpp"   // optimiser arithmetic and problem shapes
+#include "irm_dispatch.hpp"     // dispatch_d, dispatch_t, launch_lds
+#include "irm_launch_decl.hpp"  // per-shape launcher declarations, IRM_FIX_SHAPES, IRM_EXTERN_*
 
 namespace irm {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// The kernels are compiled with -ffp-contract=off (build.py): every fused multiply-add is written
-// as one, so the arithmetic does not depend on the compiler's contraction choices.
-__device__ __forceinline__ f32x2 pkfma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-
-// ------------------------------------------------------------ LDS planning
-
-// ------------------------------------------------------------ wave helpers
-// DPP row reductions (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror,
-// row_mirror) leave each 16-lane row reduced in all its lanes; the four
-// rows are then combined from v_readlane (uniform result, no LDS).
-// Every control used here is an in-row permutation (no lane reads outside its row), so the old value
-// is never kept: mov_dpp (old undefined, bound_ctrl) lets the compiler fold the move into the consuming
-// VALU op as a DPP source (v_add_f32_dpp …) instead of v_mov_b32 + v_mov_b32_dpp + the op.
-template <int CTRL>
-__device__ __forceinline__ float dppf(float v) {
-    static_assert(CTRL == 0xB1 || CTRL == 0x4E || CTRL == 0x141 || CTRL == 0x140, "in-row permutations only");
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-template <int CTRL>
-__device__ __forceinline__ int dppi(int v) {
-    static_assert(CTRL == 0xB1 || CTRL == 0x4E || CTRL == 0x141 || CTRL == 0x140, "in-row permutations only");
-    return __builtin_amdgcn_mov_dpp(v, CTRL, 0xF, 0xF, true);
-}
-// s + (row_bcast:15 of s) in rows 1 and 3 (ROW = 15), s + (row_bcast:31 of s) in rows 2 and 3 (ROW = 31);
-// the other rows keep s.  As one v_add_f32_dpp (the compiler's DPP combine leaves the float add with a
-// partial row mask as a v_mov_b32_dpp + v_add_f32 pair); s_nop 1: the VALU-write → DPP-read hazard.
-template <int ROW>
-__device__ __forceinline__ float bcast_add(float s) {
-    static_assert(ROW == 15 || ROW == 31, "row broadcasts");
-    if constexpr (ROW == 15)
-        asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf" : "+v"(s));
-    else
-        asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf" : "+v"(s));
-    return s;
-}
-// max of floats that are ≥ +0 or −inf, on their bit patterns (signed-int order = float order there):
-// no NaN canonicalisation, and the DPP move folds into v_max_i32_dpp
-__device__ __forceinline__ float maxpos(float a, float b) {
-    return __int_as_float(max(__float_as_int(a), __float_as_int(b)));
-}
-__device__ __forceinline__ float lanef(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ float wred_sum(float v) {
-    v += dppf<0xB1>(v);
-    v += dppf<0x4E>(v);
-    v += dppf<0x141>(v);
-    v += dppf<0x140>(v);
-    return (lanef(v, 0) + lanef(v, 16)) + (lanef(v, 32) + lanef(v, 48));
-}
-__device__ __forceinline__ float wred_max(float v) {
-    v = fmaxf(v, dppf<0xB1>(v));
-    v = fmaxf(v, dppf<0x4E>(v));
-    v = fmaxf(v, dppf<0x141>(v));
-    v = fmaxf(v, dppf<0x140>(v));
-    return fmaxf(fmaxf(lanef(v, 0), lanef(v, 16)), fmaxf(lanef(v, 32), lanef(v, 48)));
-}
-__device__ __forceinline__ float wred_min(float v) {
-    v = fminf(v, dppf<0xB1>(v));
-    v = fminf(v, dppf<0x4E>(v));
-    v = fminf(v, dppf<0x141>(v));
-    v = fminf(v, dppf<0x140>(v));
-    return fminf(fminf(lanef(v, 0), lanef(v, 16)), fminf(lanef(v, 32), lanef(v, 48)));
-}
-// max with first-index tie break (jnp.argmax, trajectory.py:97)
-__device__ __forceinline__ void amax_step(float& v, int& i, float ov, int oi) {
-    if (ov > v || (ov == v && oi < i)) {
-        v = ov;
-        i = oi;
-    }
-}
-template <int CTRL>
-__device__ __forceinline__ void amax_dpp(float& v, int& i) {
-    float ov = dppf<CTRL>(v);
-    int oi = dppi<CTRL>(i);
-    amax_step(v, i, ov, oi);
-}
-__device__ __forceinline__ void wred_argmax(float& v, int& i) {
-    amax_dpp<0xB1>(v, i);
-    amax_dpp<0x4E>(v, i);
-    amax_dpp<0x141>(v, i);
-    amax_dpp<0x140>(v, i);
-    float bv = lanef(v, 0);
-    int bi = __builtin_amdgcn_readlane(i, 0);
-#pragma unroll
-    for (int r = 16; r < 64; r += 16) amax_step(bv, bi, lanef(v, r), __builtin_amdgcn_readlane(i, r));
-    v = bv;
-    i = bi;
-}
-
-// ---------------------------------------------------- phase profiler (diag)
-// Built with -DIRM_PHASE_PROFILE: thread 0 of each workgroup accumulates the
-// shader-clock cycles (s_memtime) between consecutive stamps per phase into
-// P.prof[block][phase].  In the shipped build every stamp is empty.
-struct Prof {
-#ifdef IRM_PHASE_PROFILE
-    unsigned long long last, acc[kProfPhases];
-    __device__ __forceinline__ void init() {
-        last = __builtin_amdgcn_s_memtime();
-#pragma unroll
-        for (int i = 0; i < kProfPhases; ++i) acc[i] = 0;
-    }
-    __device__ __forceinline__ void stamp(int ph) {
-        unsigned long long now = __builtin_amdgcn_s_memtime();
-        acc[ph] += now - last;
-        last = now;
-    }
-    __device__ __forceinline__ void count(int ph, bool c) {
-        if (c) acc[ph] += 1;
-    }
-    __device__ __forceinline__ void flush(unsigned long long* out) {
-        if (out)
-            for (int i = 0; i < kProfPhases; ++i) out[(size_t)blockIdx.x * kProfPhases + i] = acc[i];
-    }
-#else
-    __device__ __forceinline__ void init() {}
-    __device__ __forceinline__ void stamp(int) {}
-    __device__ __forceinline__ void count(int, bool) {}
-    __device__ __forceinline__ void flush(unsigned long long*) {}
-#endif
-};
-#ifdef IRM_ISA_MARKS  // analysis builds: phase markers in the emitted assembly
-#define IRM_STAMP(ph) asm volatile("; IRM_PHASE " #ph)
-#define IRM_COUNT(ph, c)
-#else
-#define IRM_STAMP(ph)                         \
-    do {                                      \
-        if (threadIdx.x == 0) prof.stamp(ph); \
-    } while (0)
-#define IRM_COUNT(ph, c)                          \
-    do {                                          \
-        if (threadIdx.x == 0) prof.count(ph, c);  \
-    } while (0)
-#endif
-
-// ---------------------------------------------------------- MFMA contraction
-// D layout of 16x16x4: lane l holds rows 4*(l>>4)+i, column l&15.
-// Callers keep every tile inside the buffer (row extents are multiples of 16).
-__device__ __forceinline__ void store_tile(float* out, int tile, f32x4 acc, unsigned colmask) {
-    const int lane = threadIdx.x & 63;
-    const int col = lane & 15;
-    if (!((colmask >> col) & 1u)) return;
-    float* o = out + (tile * 16 + 4 * (lane >> 4)) * kLd + col;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i * kLd] = acc[i];
-}
-
-// ------------------------------------------------ per-waypoint physics
-// sin/cos for robot.py's joint angles: Cody-Waite reduction by π/2 (3-part
-// split, fma) and the cephes single-precision minimax polynomials on
-// [−π/4, π/4]; branch-free.  Measured against double for |x| ≤ 1e4 (tests/test_physics_host.py, 1.1e8
-// angles): at most 1.56 ulp of the correctly rounded result, for sin and for cos, next to odd multiples of
-// π/4 (1.3 / 1.4 ulp next to multiples of π/2); asserted < 2 ulp.  |x| > 1e4 rad falls back to sincosf.
-__device__ __forceinline__ void sincos_poly(float x, float& sn, float& cs) {
-    // k = round(x·2/π) by the 1.5·2²³ shifter: one fma rounds the exact product to an integer (ties to
-    // even), whose low bits are k's two's-complement bits in t's mantissa (|k| < 2²² here); kf = k as a
-    // float.  (rintf(fl(x·2/π)) differs only where x·2/π lies within an ulp of a half-integer — then r
-    // sits at ±π/4 either way, inside the polynomials' accurate range.)
-    const float t = fmaf(x, 0.636619772f, 12582912.0f);
-    const float kf = t - 12582912.0f;
-    float r = fmaf(kf, -1.57079637050628662109375f, x);
-    r = fmaf(kf, 4.371138828673793e-08f, r);
-    r = fmaf(kf, 1.7151245100058819e-15f, r);
-    const float z = r * r;
-    const float sp = fmaf(r * z, fmaf(z, fmaf(z, -1.9515295891e-4f, 8.3321608736e-3f), -1.6666654611e-1f), r);
-    const float cp = fmaf(z * z, fmaf(z, fmaf(z, 2.443315711809948e-5f, -1.388731625493765e-3f), 4.166664568298827e-2f),
-                          fmaf(-0.5f, z, 1.0f));
-    // quadrant q = kf mod 4: swap on odd q, sin negated for q ∈ {2, 3}, cos for q ∈ {1, 2} — the sign
-    // flips as bit 1 of q (resp. q + 1) moved to the sign bit (an xor; −x and the flip agree bit for bit)
-    const int qi = __float_as_int(t);  // k mod 4 in the low bits
-    const float s0 = (qi & 1) ? cp : sp;
-    const float c0 = (qi & 1) ? sp : cp;
-    sn = __uint_as_float(__float_as_uint(s0) ^ (((unsigned)qi << 30) & 0x80000000u));
-    cs = __uint_as_float(__float_as_uint(c0) ^ (((unsigned)(qi + 1) << 30) & 0x80000000u));
-}
-__device__ __forceinline__ void sincos_fast(float x, float& sn, float& cs) {
-    if (__builtin_expect(fabsf(x) > 1.0e4f, 0)) {
-        sincosf(x, &sn, &cs);
-        return;
-    }
-    sincos_poly(x, sn, cs);
-}
-
-template <int D>
-struct WP {
-    float cv, gx, gy;        // obstacle potential and its gradient at the end effector
-    float jp, jv;            // masked joint-position / joint-velocity penalty terms (LEAN: Σ zm², Σ zvm²)
-    float tx, tn, va;        // max/min joint position, max |joint velocity|
-    float jx[D], jy[D];      // end-effector Jacobian row
-    float fx, fy;            // end-effector position (eval_waypoint<…, POT = false>: potential not yet added)
-    float zm[D], zvm[D];     // LEAN: masked (q − μ)/σ_q and v/v_max (0 where the limit mask is off)
-};
-
-// End-effector goal (P.task, include/irm.h): what the end row's terms need of a waypoint's evaluation — the
-// end-effector position f the evaluation itself formed and the end effector's Jacobian J_ee (with WHOLE,
-// WP::jx holds the whole-robot gradient instead).
-template <int D>
-struct EE {
-    float fx, fy;
-    float jx[D], jy[D];
-};
-
-// The end row's terms of an end-effector goal from its evaluation, in the fp32 order include/irm.h defines:
-//   e = f − p,  r² = fmaf(e_y, e_y, e_x·e_x),  ge[d] = fmaf(J_y[d], e_y, J_x[d]·e_x)  (= J_eeᵀ·e)
-// r² takes the place of ‖T[N−1] − g‖² (loss, constraint) and ge that of T[N−1] − g (gradient input a).
-template <int D>
-__device__ __forceinline__ void task_end_row(const EE<D>& ee, float px, float py, float (&ge)[D], float& r2) {
-    const float ex = ee.fx - px, ey = ee.fy - py;
-    r2 = fmaf(ey, ey, ex * ex);
-#pragma unroll
-    for (int d = 0; d < D; ++d) ge[d] = fmaf(ee.jy[d], ey, ee.jx[d] * ex);
-}
-
-// Via-points (P.via, include/irm.h): the via-point this lane's row n carries — −1 none, else v + 4·cartesian[v]
-// (rows are strictly increasing: at most one matches).  Unrolled over the table, so every read of the
-// kernel-argument arrays has a constant index.
-__device__ __forceinline__ int via_code(const KParams& P, int n) {
-    int code = -1;
-#pragma unroll
-    for (int i = 0; i < IRM_MAX_VIA; ++i)
-        if (i < P.n_via && n == P.via_row[i]) code = i + 4 * (P.via_cart[i] != 0 ? 1 : 0);
-    return code;
-}
-// The via row's terms (r², ge) of via-point `code` of problem b from the row's waypoint q and its evaluation's
-// ee, in the fp32 order include/irm.h defines.  FMA: the joint distance accumulates as the calling kernel
-// accumulates row N−1 against the joint goal — fmaf(e, e, a) in k_optimize, a += e·e in k_forward.
-template <int D, bool FMA>
-__device__ __forceinline__ void via_row_terms(const KParams& P, size_t b, int code, const float (&q)[D],
-                                              const EE<D>& ee, float (&ge)[D], float& r2) {
-    const float* c = P.via_target + (b * (size_t)P.n_via + (size_t)(code & 3)) * D;
-    if (code & 4) {
-        if constexpr (D >= 2) task_end_row<D>(ee, c[0], c[1], ge, r2);  // (D = 1: refused by the host)
-        return;
-    }
-    float a = 0.f;
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        const float e = q[d] - c[d];
-        ge[d] = e;
-        if constexpr (FMA) a = fmaf(e, e, a);
-        else a += e * e;
-    }
-    r2 = a;
-}
-
-// robot.py:29-36 (fk), 75-87 (jacobian); environment.py:46-58
-// (compute_cost_vg); trajectory.py:215-227, 245-255 (penalty elements).
-// WHOLE: the potential is summed over every joint position p_j = fk_joint_j
-// (robot.py:39-72; DevBlog-Theme/blog-post.html:491-498) instead of the end
-// effector only.  Its gradient w.r.t. angle k is Σ_{l≥k} (X_l·GX_l + Y_l·GY_l)
-// with (X_l, Y_l) = L_l·(−sin c_l, cos c_l) and GX_l = Σ_{j≥l} ∂cost/∂p_j; it is
-// returned as w.jx (with w.gx = 1, w.jy = w.gy = 0) so grad_waypoint is shared.
-// POT = false (end-effector cost only): everything but the obstacle potential, whose inputs are left
-// in w.fx / w.fy (potential_pair evaluates two waypoints' potentials in one pass over the obstacles).
-// LEAN evaluations keep zm / zvm for the gradient inputs at D ≤ 3; at D = 7 the 14 values live across
-// the evaluation barrier pushed the spill-free 7-DoF bench kernels into scratch, so the gradient inputs
-// recompute them there (lean_pen: the same arithmetic, the same values)
-template <int D>
-constexpr bool kLeanKeep = D <= 3;
-template <int D>
-__device__ __forceinline__ void lean_pen(const KParams& P, const float (&q)[D], const float (&v)[D], float (&zm)[D],
-                                         float (&zvm)[D]) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        const float z = (q[d] - P.mean_pos) * P.inv_std_pos;
-        const bool m = (q[d] > P.thr_hi) || (q[d] < P.thr_lo);
-        const float zv = v[d] * P.inv_vmax;
-        const bool mv = fabsf(v[d]) > P.thr_v;
-        zm[d] = m ? z : 0.f;  // (cvdl off: the host's thresholds make every mask true)
-        zvm[d] = mv ? zv : 0.f;
-    }
-}
-
-// LEAN (the optimiser kernels): the penalty terms in the form the loss and the gradient inputs share —
-// zm = mask·(q − μ)/σ_q and zvm = mask·v/v_max per joint, w.jp = Σ zm², w.jv = Σ zvm² (the ½ and the
-// 1/N of trajectory.py:215-227, 245-255 go into the per-trajectory weights, grad_waypoint_lean); the
-// host-API kernels keep the reference's element order (½·z² per element, summed).
-// MOVING: every obstacle drifts at a constant velocity over the plan; the lane's waypoint lies at plan time
-// tau and sees obstacle o at fmaf(tau, w_o, p_o) per coordinate — one packed FMA per coordinate pair of an
-// obstacle pair, from the velocity table `vel` (LDS, stage_obstacles' layout; sentinel velocity 0, so the
-// padding stays at 1e20 and adds exactly 0).  From there on the arithmetic is the static one's; a zero
-// velocity gives the static result to the bit (fmaf(tau, 0, p) = p).
-// TASK: *ee receives f and J_ee as formed here (no second FK); nothing else changes.
-template <int D, bool WHOLE = false, bool POT = true, bool LEAN = false, bool MOVING = false, bool TASK = false>
-__device__ __forceinline__ void eval_waypoint(const KParams& P, const float (&q)[D], const float (&v)[D],
-                                              const float* __restrict__ ob, WP<D>& w,
-                                              const f32x4* oreg = nullptr,  // oreg: the 12-obstacle
-                                                                            // table held in VGPRs
-                                              const float* __restrict__ vel = nullptr, float tau = 0.f,
-                                              EE<D>* ee = nullptr) {
-    float fx = 0.f, fy = 0.f, Sx = 0.f, Sy = 0.f;
-    float xs[D], ys[D], px[D], py[D], cum[D], snv[D], csv[D];
-    bool big = false;
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        cum[d] = d ? cum[d - 1] + q[d] : q[d];
-        big |= fabsf(cum[d]) > 1.0e4f;
-    }
-    // One wave-uniform branch for all joints: the D polynomial chains share a basic block (the
-    // scheduler interleaves them); a wave with any |angle| > 1e4 takes the per-lane form, whose
-    // small-angle lanes compute the same polynomial, so every lane's value is that of sincos_fast.
-#ifdef IRM_X_NOSC
-    big = true;
-#endif
-    if (__builtin_expect(__ballot(big) != 0ull, 0)) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) sincos_fast(cum[d], snv[d], csv[d]);
-    } else {
-#pragma unroll
-        for (int d = 0; d < D; ++d) sincos_poly(cum[d], snv[d], csv[d]);
-    }
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        const float sn = snv[d], cs = csv[d];
-        fx = fmaf(P.link[d], cs, fx);
-        fy = fmaf(P.link[d], sn, fy);
-        px[d] = fx;
-        py[d] = fy;
-        xs[d] = -(P.link[d] * sn);
-        ys[d] = P.link[d] * cs;
-        Sx = d ? Sx + xs[d] : xs[d];
-        Sy = d ? Sy + ys[d] : ys[d];
-    }
-    // Obstacles are staged in LDS in pairs (x_a, x_b, y_a, y_b), padded to a multiple of 4
-    // with sentinels at (1e20, 1e20): r² overflows to +inf, rcp → 0, so a sentinel adds
-    // exactly 0.  Two obstacles per packed-fp32 instruction; the even- and odd-numbered
-    // obstacles accumulate separately and are added at the end.
-    const f32x4* o4 = reinterpret_cast<const f32x4*>(ob);
-    const int nq = (P.O + 3) >> 2;
-    // obstacle pair i (x_a, x_b, y_a, y_b) at this lane's time
-    auto pair_at = [&](int i) -> f32x4 {
-        f32x4 p = o4[i];
-        if constexpr (MOVING) {
-            const f32x4 wv = reinterpret_cast<const f32x4*>(vel)[i];
-            const f32x2 t2 = {tau, tau};
-            p.xy = pkfma(t2, wv.xy, p.xy);
-            p.zw = pkfma(t2, wv.zw, p.zw);
-        }
-        return p;
-    };
-    // Per pair of obstacles: e = 1 + dx² + dy² (= 2·den), u = rcp(e); the potential's constants are
-    // applied once at the end: cost = 0.8/den = 1.6·Σu, ∂cost/∂f = −0.8·d/den² = −3.2·Σ d·u².
-    auto potential = [&](float x, float y, float& cv, float& ax, float& ay) {
-        f32x2 cv2 = {0.f, 0.f}, ax2 = {0.f, 0.f}, ay2 = {0.f, 0.f};
-        const f32x2 fx2 = {x, x}, fy2 = {y, y}, one = {1.f, 1.f};
-        auto pair2 = [&](f32x2 ox, f32x2 oy) {
-            const f32x2 dx = fx2 - ox, dy = fy2 - oy;
-            const f32x2 e = pkfma(dy, dy, pkfma(dx, dx, one));
-            const f32x2 u = {__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
-            cv2 += u;
-            const f32x2 u2 = u * u;
-            ax2 = pkfma(dx, u2, ax2);
-            ay2 = pkfma(dy, u2, ay2);
-        };
-#ifdef IRM_X_NOOBS
-        if (false) {
-#else
-        if (nq == 3) {  // 9-12 obstacles (the reference's 11): one straight-line block, all 12 rcps
-                        // issued back to back, then the sums in pair2's order
-#endif
-            f32x2 dx[6], dy[6], u[6];
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                f32x4 p;
-                if constexpr (MOVING) p = pair_at(i);
-                else p = oreg ? oreg[i] : o4[i];
-                dx[i] = fx2 - p.xy;
-                dy[i] = fy2 - p.zw;
-                const f32x2 e = pkfma(dy[i], dy[i], pkfma(dx[i], dx[i], one));
-                u[i] = f32x2{__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
-            }
-            // (the sums start from the first pair, not from +0: the same values, two instructions fewer)
-            cv2 = u[0];
-            ax2 = dx[0] * (u[0] * u[0]);
-            ay2 = dy[0] * (u[0] * u[0]);
-#pragma unroll
-            for (int i = 1; i < 6; ++i) {
-                cv2 += u[i];
-                const f32x2 u2 = u[i] * u[i];
-                ax2 = pkfma(dx[i], u2, ax2);
-                ay2 = pkfma(dy[i], u2, ay2);
-            }
-        } else {
-            for (int c = 0; c < nq; ++c) {
-                f32x4 p0, p1;
-                if constexpr (MOVING) {
-                    p0 = pair_at(2 * c);
-                    p1 = pair_at(2 * c + 1);
-                } else {
-                    p0 = o4[2 * c];
-                    p1 = o4[2 * c + 1];
-                }
-                pair2(p0.xy, p0.zw);
-                pair2(p1.xy, p1.zw);
-            }
-        }
-        cv = 1.6f * (cv2.x + cv2.y);
-        ax = -3.2f * (ax2.x + ax2.y);
-        ay = -3.2f * (ay2.x + ay2.y);
-    };
-    if constexpr (TASK) {
-        ee->fx = fx;
-        ee->fy = fy;
-    }
-    if constexpr (!WHOLE) {
-        float Cx = 0.f, Cy = 0.f;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            Cx = d ? Cx + xs[d] : xs[d];
-            Cy = d ? Cy + ys[d] : ys[d];
-            w.jx[d] = (xs[d] + Sx) - Cx;
-            w.jy[d] = (ys[d] + Sy) - Cy;
-            if constexpr (TASK) {
-                ee->jx[d] = w.jx[d];
-                ee->jy[d] = w.jy[d];
-            }
-        }
-        if constexpr (POT) {
-            potential(fx, fy, w.cv, w.gx, w.gy);
-        } else {
-            w.fx = fx;
-            w.fy = fy;
-        }
-    } else {
-        if constexpr (TASK) {  // J_ee in the order of the end-effector variant above
-            float Cx = 0.f, Cy = 0.f;
-#pragma unroll
-            for (int d = 0; d < D; ++d) {
-                Cx = d ? Cx + xs[d] : xs[d];
-                Cy = d ? Cy + ys[d] : ys[d];
-                ee->jx[d] = (xs[d] + Sx) - Cx;
-                ee->jy[d] = (ys[d] + Sy) - Cy;
-            }
-        }
-        float cvt = 0.f, gxj[D], gyj[D];
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            float cvj;
-            potential(px[j], py[j], cvj, gxj[j], gyj[j]);
-            cvt += cvj;
-        }
-        float GX = 0.f, GY = 0.f, acc = 0.f;
-#pragma unroll
-        for (int l = D - 1; l >= 0; --l) {
-            GX += gxj[l];
-            GY += gyj[l];
-            acc = fmaf(xs[l], GX, fmaf(ys[l], GY, acc));
-            w.jx[l] = acc;
-            w.jy[l] = 0.f;
-        }
-        w.cv = cvt;
-        w.gx = 1.f;
-        w.gy = 0.f;
-    }
-    float jp = 0.f, jv = 0.f, tx = -INFINITY, tn = INFINITY, va = 0.f;
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        const float z = (q[d] - P.mean_pos) * P.inv_std_pos;
-        const bool m = (q[d] > P.thr_hi) || (q[d] < P.thr_lo);
-        const float zv = v[d] * P.inv_vmax;
-        const bool mv = fabsf(v[d]) > P.thr_v;
-        if constexpr (LEAN) {
-            const float zm = m ? z : 0.f, zvm = mv ? zv : 0.f;  // (cvdl: folded into the thresholds)
-            if constexpr (kLeanKeep<D>) {
-                w.zm[d] = zm;
-                w.zvm[d] = zvm;
-            }
-            jp = fmaf(zm, zm, jp);
-            jv = fmaf(zvm, zvm, jv);
-        } else {
-            jp += m ? 0.5f * (z * z) : 0.f;
-            jv += mv ? 0.5f * (zv * zv) : 0.f;
-        }
-        tx = fmaxf(tx, q[d]);
-        tn = fminf(tn, q[d]);
-        va = fmaxf(va, fabsf(v[d]));
-    }
-    w.jp = jp;
-    w.jv = jv;
-    w.tx = tx;
-    w.tn = tn;
-    w.va = va;
-}
-
-// The obstacle potential of two waypoints (w0.fx/fy, w1.fx/fy) in one pass over the LDS obstacle table:
-// each obstacle pair is loaded once and both waypoints' terms are formed from it (independent chains
-// that interleave).  Per waypoint the arithmetic and the accumulation order are eval_waypoint's.
-template <int D>
-__device__ __forceinline__ void potential_pair(const KParams& P, const float* __restrict__ ob, WP<D>& w0, WP<D>& w1) {
-    const f32x4* o4 = reinterpret_cast<const f32x4*>(ob);
-    const int nq = (P.O + 3) >> 2;
-    f32x2 cv0 = {0.f, 0.f}, ax0 = {0.f, 0.f}, ay0 = {0.f, 0.f}, cv1 = cv0, ax1 = cv0, ay1 = cv0;
-    const f32x2 x0 = {w0.fx, w0.fx}, y0 = {w0.fy, w0.fy}, x1 = {w1.fx, w1.fx}, y1 = {w1.fy, w1.fy};
-    const f32x2 one = {1.f, 1.f};
-    auto pair2 = [&](const f32x2& fx2, const f32x2& fy2, f32x2 ox, f32x2 oy, f32x2& cv2, f32x2& ax2, f32x2& ay2) {
-        const f32x2 dx = fx2 - ox, dy = fy2 - oy;
-        const f32x2 e = pkfma(dy, dy, pkfma(dx, dx, one));
-        const f32x2 u = {__builtin_amdgcn_rcpf(e.x), __builtin_amdgcn_rcpf(e.y)};
-        cv2 += u;
-        const f32x2 u2 = u * u;
-        ax2 = pkfma(dx, u2, ax2);
-        ay2 = pkfma(dy, u2, ay2);
-    };
-    for (int c = 0; c < nq; ++c) {
-        const f32x4 p0 = o4[2 * c], p1 = o4[2 * c + 1];
-        pair2(x0, y0, p0.xy, p0.zw, cv0, ax0, ay0);
-        pair2(x1, y1, p0.xy, p0.zw, cv1, ax1, ay1);
-        pair2(x0, y0, p1.xy, p1.zw, cv0, ax0, ay0);
-        pair2(x1, y1, p1.xy, p1.zw, cv1, ax1, ay1);
-    }
-    w0.cv = 1.6f * (cv0.x + cv0.y);
-    w0.gx = -3.2f * (ax0.x + ax0.y);
-    w0.gy = -3.2f * (ay0.x + ay0.y);
-    w1.cv = 1.6f * (cv1.x + cv1.y);
-    w1.gx = -3.2f * (ax1.x + ax1.y);
-    w1.gy = -3.2f * (ay1.x + ay1.y);
-}
-
-// eval_waypoint with the cost variant chosen at run time (host-API kernels, DynShape optimiser).
-// vel / tau: the moving variant (P.moving; vel the LDS velocity table behind ob's, tau the lane's time)
-// TASK: *ee receives f and J_ee (eval_waypoint; the caller decides at run time whether it uses them)
-template <int D, bool TASK = false>
-__device__ __forceinline__ void eval_waypoint_rt(const KParams& P, const float (&q)[D], const float (&v)[D],
-                                                 const float* __restrict__ ob, WP<D>& w,
-                                                 const float* __restrict__ vel = nullptr, float tau = 0.f,
-                                                 EE<D>* ee = nullptr) {
-    if (P.moving) {
-        if (P.whole_robot) eval_waypoint<D, true, true, false, true, TASK>(P, q, v, ob, w, nullptr, vel, tau, ee);
-        else eval_waypoint<D, false, true, false, true, TASK>(P, q, v, ob, w, nullptr, vel, tau, ee);
-        return;
-    }
-    if (P.whole_robot) eval_waypoint<D, true, true, false, false, TASK>(P, q, v, ob, w, nullptr, nullptr, 0.f, ee);
-    else eval_waypoint<D, false, true, false, false, TASK>(P, q, v, ob, w, nullptr, nullptr, 0.f, ee);
-}
-
-// Gradient inputs a (→ Kᵀ) and b (→ dKᵀ) of one waypoint, trajectory.py:91-126
-// (obstacle), 191-212 (start/goal), 231-242 / 259-268 (joint limits).
-// task_row: this lane is row N−1 of an end-effector-goal call and g holds ge = J_eeᵀ·(f − p)
-// (task_end_row), which takes the place of q − g.
-template <int D>
-__device__ __forceinline__ void grad_waypoint(const KParams& P, const WP<D>& w, const float (&q)[D],
-                                              const float (&v)[D], int n, int idx, float lsg, float ljl,
-                                              const float (&s)[D], const float (&g)[D], float (&a)[D],
-                                              float (&b)[D], bool task_row = false, bool via_row = false) {
-    // via_row: this lane's row (in 1 … N−2) carries a via-point and g holds its ge (via_row_terms); the position
-    // term only — a via row's velocity is free
-    const int N = P.N;
-    const float wt = (n == idx ? P.lam_max : 0.f) + P.one_m_lmax * P.invN;
-    const float wx = wt * w.gx, wy = wt * w.gy;
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        float sgp = 0.f, sgv = 0.f;
-        if (n == 0) {
-            sgp = q[d] - s[d];
-            sgv = v[d];
-        }
-        if (n == N - 1) {
-            sgp = task_row ? g[d] : q[d] - g[d];
-            sgv = v[d];
-        }
-        if (via_row) sgp = g[d];
-        float jpg = 0.f, jvg = 0.f;
-        const bool m = (q[d] > P.thr_hi) || (q[d] < P.thr_lo);
-        if (m) jpg = ((q[d] - P.mean_pos) * P.inv_std2) * P.invN;
-        const bool mv = fabsf(v[d]) > P.thr_v;
-        if (mv) jvg = (v[d] * P.inv_vmax2) * P.invN;
-        a[d] = fmaf(ljl, jpg, fmaf(lsg, sgp, fmaf(wx, w.jx[d], wy * w.jy[d])));
-        b[d] = fmaf(lsg, sgv, ljl * jvg);
-    }
-}
-
-// Per-trajectory weights of the LEAN evaluation (uniform; ljl changes with the outer iteration):
-// the loss's mean / penalty terms u = c_mean·cv + c_pen·(Σzm² + Σzvm²) (trajectory.py:85-87, 281 with
-// ½ and 1/N folded), the gradient's penalty slopes k_pos = λjl/(σ_q·N), k_vel = λjl/(v_max·N)
-// (trajectory.py:231-242, 259-268: (q − μ)/σ_q²/N = zm·(1/σ_q)/N).
-struct LeanW {
-    float c_mean, c_pen, k_pos, k_vel;
-};
-__device__ __forceinline__ LeanW lean_weights(const KParams& P, float ljl) {
-    LeanW c;
-    c.c_mean = P.one_m_lmax * P.invN;
-    c.c_pen = (0.5f * ljl) * P.invN;
-    c.k_pos = (ljl * P.inv_std_pos) * P.invN;
-    c.k_vel = (ljl * P.inv_vmax) * P.invN;
-    return c;
-}
-
-// Gradient inputs a, b of one waypoint from a LEAN evaluation (grad_waypoint's terms, the penalty
-// masks and normalised deviations reused from the evaluation).  lsg_ep = λsg on rows 0 and N−1, else
-// 0 (per lane); tg the row's start / goal.
-// TASK (k_optimize<DynShape<D>>): on the lane with task_row — row N−1 of an end-effector-goal launch — tg
-// holds ge = J_eeᵀ·(f − p) (task_end_row), which takes the place of q − tg.  lsg_pos: the weight of the position
-// term — lsg_ep on every row but a via row (via_row_terms: task_row set, tg its ge), where it is λsg while
-// lsg_ep, which also weighs v[d], stays 0: a via row's velocity is free.
-template <int D, bool TASK = false>
-__device__ __forceinline__ void grad_waypoint_lean(const KParams& P, const WP<D>& w, const float (&q)[D],
-                                                   const float (&v)[D], bool isidx, float lsg_ep,
-                                                   const LeanW& c, const float (&tg)[D], float (&a)[D],
-                                                   float (&b)[D], bool task_row = false, float lsg_pos = 0.f) {
-    const float wt = (isidx ? P.lam_max : 0.f) + c.c_mean;
-    const float wx = wt * w.gx, wy = wt * w.gy;
-    float zm[D], zvm[D];
-    if constexpr (kLeanKeep<D>) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            zm[d] = w.zm[d];
-            zvm[d] = w.zvm[d];
-        }
-    } else {
-        lean_pen<D>(P, q, v, zm, zvm);
-    }
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        float sgp = q[d] - tg[d];
-        float lp = lsg_ep;
-        if constexpr (TASK) {
-            sgp = task_row ? tg[d] : sgp;
-            lp = lsg_pos;
-        }
-        a[d] = fmaf(c.k_pos, zm[d], fmaf(lp, sgp, fmaf(wx, w.jx[d], wy * w.jy[d])));
-        b[d] = fmaf(lsg_ep, v[d], c.k_vel * zvm[d]);
-    }
-}
-
-// Result of one cost evaluation of one trajectory (reduced over waypoints).
-struct EvalOut {
-    float loss, ds, dg, vs, vg, tmax, tmin, vabs;
-    int idx;
-};
-
-// Wave-reduce this lane's waypoint terms; lane 0 of each wave stores the
-// partials, the lanes of rows 0 / N−1 store the start/goal terms.  Must be
-// reached by the whole wave (a wave never straddles two trajectories).
-// kRedW: words per wave of `red`, the eight partials — plan_head gives the region kMaxWaves·8 words and `sg`
-// follows it directly, so a wider stride would put the partials of a 1024-thread workgroup's last waves onto
-// the start/goal words (four N = 256 or two N = 512 trajectories in one workgroup).
-constexpr int kRedW = 8;
-template <int D>
-__device__ __forceinline__ void eval_partials(const KParams& P, bool live, const WP<D>& w, int n, int wave,
-                                              const float (&q)[D], const float (&v)[D], const float (&s)[D],
-                                              const float (&g)[D], float* red, float* sg, int t,
-                                              bool task_row = false, float r2 = 0.f) {  // task_row: row N−1 of
-                                              // an end-effector-goal call stores r² = ‖f − p‖² (task_end_row)
-    float cmax = live ? w.cv : -INFINITY;
-    int cidx = live ? n : 0x7fffffff;
-    wred_argmax(cmax, cidx);
-    const float csum = wred_sum(live ? w.cv : 0.f);
-    const float jps = wred_sum(live ? w.jp : 0.f);
-    const float jvs = wred_sum(live ? w.jv : 0.f);
-    const float tx = wred_max(live ? w.tx : -INFINITY);
-    const float tn = wred_min(live ? w.tn : INFINITY);
-    const float va = wred_max(live ? w.va : 0.f);
-    if ((threadIdx.x & 63) == 0) {
-        float* r = red + wave * kRedW;
-        r[0] = cmax;
-        r[1] = __int_as_float(cidx);
-        r[2] = csum;
-        r[3] = jps;
-        r[4] = jvs;
-        r[5] = tx;
-        r[6] = tn;
-        r[7] = va;
-    }
-    if (live && (n == 0 || n == P.N - 1)) {  // trajectory.py:183-204 rows 0 and N−1
-        float a = 0.f, bb = 0.f;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            const float e = q[d] - (n == 0 ? s[d] : g[d]);
-            a += e * e;
-            bb += v[d] * v[d];
-        }
-        if (task_row) a = r2;
-        sg[t * 4 + (n == 0 ? 0 : 2)] = a;
-        sg[t * 4 + (n == 0 ? 1 : 3)] = bb;
-    }
-}
-
-// Combine the trajectory's wave partials (fixed order) into loss + stats.
-// viaw / nvia: the trajectory's via words r_v² (a via launch), which join the start/goal position sum in index
-// order after its two terms (include/irm.h).
-__device__ __forceinline__ EvalOut eval_finalize(const KParams& P, const float* red, const float* sg, int t,
-                                                 int wave0, int nwt, float lsg, float ljl,
-                                                 const float* viaw = nullptr, int nvia = 0) {
-    const float* r = red + wave0 * kRedW;
-    float cmax = r[0];
-    int cidx = __float_as_int(r[1]);
-    float csum = r[2], jps = r[3], jvs = r[4], tx = r[5], tn = r[6], va = r[7];
-    for (int w = 1; w < nwt; ++w) {
-        const float* q = red + (wave0 + w) * kRedW;
-        amax_step(cmax, cidx, q[0], __float_as_int(q[1]));
-        csum += q[2];
-        jps += q[3];
-        jvs += q[4];
-        tx = fmaxf(tx, q[5]);
-        tn = fminf(tn, q[6]);
-        va = fmaxf(va, q[7]);
-    }
-    const float a0 = sg[t * 4 + 0], b0 = sg[t * 4 + 1], a1 = sg[t * 4 + 2], b1 = sg[t * 4 + 3];
-    const float nN = (float)P.N;
-    float sgpc = 0.5f * a0 + 0.5f * a1;                                // trajectory.py:187
-    for (int i = 0; i < nvia; ++i) sgpc = sgpc + 0.5f * viaw[t * IRM_MAX_VIA + i];
-    const float sgvc = 0.5f * b0 + 0.5f * b1;                          // trajectory.py:203
-    const float toc = P.lam_max * cmax + P.one_m_lmax * (csum / nN);    // trajectory.py:85-87
-    EvalOut e;
-    e.loss = toc + lsg * (sgpc + sgvc) + ljl * (jps / nN + jvs / nN);  // trajectory.py:281
-    e.idx = cidx;
-    e.ds = sqrtf(a0);
-    e.dg = sqrtf(a1);
-    e.vs = sqrtf(b0);
-    e.vg = sqrtf(b1);
-    e.tmax = tx;
-    e.tmin = tn;
-    e.vabs = va;
-    return e;
-}
-
-// Obstacles into LDS: one shared set (obs_stride 0) or one per trajectory,
-// each padded to obs_pitch floats with zero-contribution sentinels.
-__host__ __device__ inline int obs_pitch(int O) { return ((O + 3) & ~3) * 2; }
-// MOVING (the kernels that have the moving variant): a moving launch (P.moving) stages the velocity table
-// behind the positions (obs_vel_offset), in the same layout and from the same shared / per-problem indexing,
-// sentinels at velocity 0.
-__host__ __device__ inline int obs_vel_offset(const KParams& P) { return (P.obs_stride ? P.TB : 1) * obs_pitch(P.O); }
-template <bool MOVING = false>
-__device__ inline void stage_obstacles(const KParams& P, int tb0, int ntb, float* obsL) {
-    const int pitch = obs_pitch(P.O), nsets = P.obs_stride ? P.TB : 1;
-    for (int e = threadIdx.x; e < nsets * pitch; e += P.BT) {
-        const int tt = e / pitch, r = e - tt * pitch;
-        // r = 4·pair + 2·coord + j  →  obstacle 2·pair + j, coordinate coord
-        const int o = 2 * (r >> 2) + (r & 1), coord = (r >> 1) & 1;
-        float val = 1.0e20f;
-        if (o < P.O) {
-            const int src = 2 * o + coord;
-            if (!P.obs_stride) val = P.obstacles[src];
-            else if (tt < ntb) val = P.obstacles[(size_t)(tb0 + tt) * P.obs_stride + src];
-        }
-        obsL[e] = val;
-    }
-    if constexpr (!MOVING) return;
-    if (!P.moving) return;
-    float* velL = obsL + nsets * pitch;
-    for (int e = threadIdx.x; e < nsets * pitch; e += P.BT) {
-        const int tt = e / pitch, r = e - tt * pitch;
-        const int o = 2 * (r >> 2) + (r & 1), coord = (r >> 1) & 1;
-        float val = 0.f;
-        if (o < P.O) {
-            const int src = 2 * o + coord;
-            if (!P.obs_stride) val = P.obs_vel[src];
-            else if (tt < ntb) val = P.obs_vel[(size_t)(tb0 + tt) * P.obs_stride + src];
-        }
-        velL[e] = val;
-    }
-}
-
-// α0 of the block's trajectories into X[n][tD+d] (rows ≥ N / unused columns 0).
-template <int D>
-__device__ void stage_alpha(const KParams& P, int tb0, int ntb, float* X, int xrows) {
-    const int N = P.N;
-    for (int e = threadIdx.x; e < xrows * 16; e += P.BT) {
-        const int n = e >> 4, c = e & 15, t = c / D, d = c - t * D;
-        float* dst = X + n * kLd + c;
-        float val = 0.f;
-        if (n < N && t < ntb) {
-            const size_t b = (size_t)(tb0 + t);
-            if (P.alpha0) {
-                val = P.alpha0[(b * N + n) * D + d];
-            } else {  // trajectory.py:73-78 via K⁻¹(1−c), K⁻¹c (linearity of solve)
-                float sj = 0.f, gj = 0.f;
-                for (int e2 = 0; e2 < D; ++e2) {
-                    sj += P.start[b * D + e2] * P.Jinv[e2 * D + d];
-                    gj += P.goal[b * D + e2] * P.Jinv[e2 * D + d];
-                }
-                val = P.uvec[n] * sj + P.wvec[n] * gj;
-            }
-        }
-        *dst = val;
-    }
-}
 
 // ------------------------------------------- correctly rounded α-space maps
 // The reference's K@α@J (trajectory.py:63-65) contracts over N waypoints with
@@ -1010,195 +237,6 @@ __device__ void grad_exact(const KParams& P, const float* __restrict__ Xa, int n
     }
 }
 
-// ------------------------------------------------------------ optimiser
-// Wave reduction of one evaluation's per-waypoint terms.
-// usum: Σ_n [(1−λmax)/N·cost_v[n] + λjl/N·(jp[n] + jv[n])], the mean-obstacle and
-// joint-limit terms of trajectory.py:281 folded into one sum; cmax with the
-// first-index argmax of jnp.argmax (trajectory.py:97) from a ballot of the lanes
-// holding the wave maximum.  tx/tn/va (constraint extrema) only when `ext`.
-// Lane 0 stores the wave's record at red[wave·8].
-__device__ __forceinline__ void ered_store(bool live, float cv, float us, float tx, float tn, float va, bool ext,
-                                           int n0, float* red, int wave) {
-    float m = live ? cv : -INFINITY, s = live ? us : 0.f;  // cv ≥ +0 (a sum of reciprocals): maxpos
-    m = maxpos(m, dppf<0xB1>(m));
-    s += dppf<0xB1>(s);
-    m = maxpos(m, dppf<0x4E>(m));
-    s += dppf<0x4E>(s);
-    m = maxpos(m, dppf<0x141>(m));
-    s += dppf<0x141>(s);
-    m = maxpos(m, dppf<0x140>(m));
-    s += dppf<0x140>(s);
-    // cross-row combine with the GFX9 row broadcasts: row_bcast:15 into rows 1 and 3, row_bcast:31 into
-    // rows 2 and 3, so lane 63 holds (r3 ∘ r2) ∘ (r1 ∘ r0) — the association of the readlane form
-    // (lanes 0, 16, 32, 48), fp addition being commutative; read back as a wave-uniform value
-    float wm, ws;
-    {
-        m = maxpos(m, __int_as_float(__builtin_amdgcn_update_dpp((int)0x80000000, __float_as_int(m), 0x142, 0xA, 0xF, false)));
-        s = bcast_add<15>(s);
-        m = maxpos(m, __int_as_float(__builtin_amdgcn_update_dpp((int)0x80000000, __float_as_int(m), 0x143, 0xC, 0xF, false)));
-        s = bcast_add<31>(s);
-        wm = lanef(m, 63);
-        ws = lanef(s, 63);
-    }
-    const unsigned long long hit = __ballot(live && cv == wm);
-    const int idx = hit ? n0 + __builtin_ctzll(hit) : 0x7fffffff;
-    float ox = 0.f, on = 0.f, oa = 0.f;
-    if (ext) {
-        ox = wred_max(live ? tx : -INFINITY);
-        on = wred_min(live ? tn : INFINITY);
-        oa = wred_max(live ? va : 0.f);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        float* q = red + wave * 8;
-        q[0] = wm;
-        q[1] = __int_as_float(idx);
-        q[2] = ws;
-        q[3] = ox;
-        q[4] = on;
-        q[5] = oa;
-    }
-}
-
-// A value the compiler may not fuse into a neighbouring operation (hipcc contracts a·b − c into
-// an fma even under `#pragma clang fp contract(off)` when the product comes from __fmul_rn).
-__device__ __forceinline__ float unfused(float x) {
-    asm("" : "+v"(x));
-    return x;
-}
-
-// a/b through a reciprocal refined by one Newton step (r = rcp_refined(b)): q = a·r, then q + (a − q·b)·r —
-// the correctly rounded quotient but in rare near-ties, in 3 VALU per quotient once r is known (the IEEE
-// division expands to ~10 with its scaling and fix-up).  The BLS trial stages form ĝ = G/‖G‖ with it
-// (optimizer_BLS.py:165); its operands are normal numbers there.
-__device__ __forceinline__ float rcp_refined(float b) {
-    const float r0 = __builtin_amdgcn_rcpf(b);
-    return fmaf(fmaf(-b, r0, 1.f), r0, r0);
-}
-__device__ __forceinline__ float div_rcp(float a, float b, float r) {
-    const float q = a * r;
-    return fmaf(fmaf(-q, b, a), r, q);
-}
-// The IEEE quotient a/b in div_rcp's 3 VALU (round 6): with r = RN(1/b), the correctly rounded reciprocal
-// (shared by every quotient of the same divisor), q = RN(a·r) is within an ulp of a/b and the fma
-// correction RN(q + (a − q·b)·r) is the correctly rounded a/b (Markstein's theorem; normal operands, and a
-// remainder a − q·b above the subnormal range).  RN(1/b) itself: one Newton step from v_rcp_f32 (faithful,
-// ≤ 1 ulp) is the correctly rounded reciprocal for every divisor but those with an all-ones mantissa
-// (b = 2^e·(2 − 2^-23)), whose RN(1/b) = 2^(−e−1)·(1 + 2^-23) has the bit pattern 0x7F000000 − bits(b) (b > 0)
-// and is selected there (branch-free; a branch here split the trial stage's block).
-// tests/test_division.py checks both statements on the host (every divisor mantissa); the IRM_DIV_CHECK build
-// counts the kernel's mismatches against __fdiv_rn (tools/div_check.py → profiles/r06_div_check.txt: 0).
-// The BLS step direction ĝ = G/‖G‖ (optimizer_BLS.py:165) uses it (b = ‖G‖ > 0, normal).
-__device__ __forceinline__ float rcp_rn_of(float b, float r) {  // r = rcp_refined(b)
-#ifdef IRM_X_RCP_OLD
-    return r;
-#else
-    const unsigned u = __float_as_uint(b);
-    return (u & 0x7fffffu) == 0x7fffffu ? __uint_as_float(0x7F000000u - u) : r;
-#endif
-}
-
-// One f32x4 of an operator fragment array through a buffer descriptor: the per-lane part of the address in
-// one VGPR (voff, shared by every load of a stream), the wave-uniform part (tile, k-quad) in soff — a
-// streamed operator holds no 64-bit address per load (the dense stages' unrolled k-loops spilled them)
-__device__ __forceinline__ f32x4 ld_frag(__amdgpu_buffer_rsrc_t r, int voff, int soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-
-// Smallest step a rounding residual is folded with (e' = −e/step): |e'| ≤ 1e-3·2^80 ≈ 1e21 stays
-// finite where a tiny BLS step (lr/‖G‖ after many rejected trials, or --gd-lr 0) would give ±inf.
-constexpr float kMinRefStep = 8.271806e-25f;  // 2^-80
-
-// One fp32 α element of the reference's GD / BLS update and its rounding residual:
-//   α' = fl(fl(c·α) − fl(lr·ĝ))                        (optimizer_GD.py:81, optimizer_BLS.py:139)
-//   e  = α' − (c·α − step·G)  exactly (to fp32 rounding of e itself), where c·[T; V] − step·F·y'
-//        is the waypoint-space update the kernel applies (ĝ = G for GD, G/‖G‖ for BLS).
-// Products and the subtraction are rounded separately (the reference's arithmetic, no fma); the
-// residuals come from fma (c·α − fl(c·α) is exact) and TwoSum.
-__device__ __forceinline__ float alpha_step(float al, float c, float lr, float gh, float step, float G, float& e) {
-    const float p1 = unfused(c * al), p2 = unfused(lr * gh);
-    const float an = unfused(p1 - p2);
-    const float ep1 = fmaf(c, al, -p1);                 // c·α − p1
-    const float bb = an - p1;                           // TwoSum(p1, −p2) = an + es
-    const float es = (p1 - (an - bb)) + (-p2 - bb);
-    const float p = unfused(step * G);
-    const float ep = fmaf(step, G, -p);                 // step·G − p
-    e = (((p - p2) - es) + ep) - ep1;                   // α' − (c·α − step·G)
-    return an;
-}
-
-// alpha_step for GD (ĝ = G, step = lr): step·G is the reference's own product p2, so its term drops.
-// α' = fl(fl(c·α) − fl(lr·G)) (optimizer_GD.py:81) and the scaled residual the direction folds in,
-// e' = −(α' − (c·α − lr·G))/lr = (c·α − α')/lr − G, as u = fl(c·α − α') (one rounding, |u| ≈ |lr·G|) and
-// e' = fl(u·(1/lr) − G) (ne = −1/lr): the residual to 2^-24 of |G| (i.e. the waypoint state to 2^-24 of a
-// step per step, below the rank-16 direction's own 1.5e-7) in two FMAs instead of TwoSum and the two
-// product errors (alpha_step_gd: 9 more VALU per component on the round's critical path)
-__device__ __forceinline__ float alpha_step_gd2(float al, float c, float lr, float G, float ne, float& eo) {
-    const float p1 = unfused(c * al), p2 = unfused(lr * G);
-    const float an = unfused(p1 - p2);
-    const float u = fmaf(c, al, -an);
-    eo = fmaf(-u, ne, -G);
-    return an;
-}
-__device__ __forceinline__ float alpha_step_gd(float al, float c, float lr, float G, float& e) {
-    const float p1 = unfused(c * al), p2 = unfused(lr * G);
-    const float an = unfused(p1 - p2);
-    const float ep1 = fmaf(c, al, -p1);
-    const float bb = an - p1;
-    const float es = (p1 - (an - bb)) + (-p2 - bb);
-    const float ep = fmaf(lr, G, -p2);                  // lr·G − p2
-    e = ((-es) + ep) - ep1;
-    return an;
-}
-
-// Operator fragments a wave keeps in VGPRs across all rounds (REGOPS).
-// Capacities mirror regops_fit (irm_kernels.hpp): a 512-thread workgroup (8 waves) keeps 4 stage-1
-// k-quads and 2 stage-2 tiles per wave (N ≤ 128 at R = 32), a 256-thread one up to 8 of each.
-
-// Problem shape of an optimiser launch.  FixShape: compile-time N / R (and everything derived,
-// incl. the LDS layout head) for the common shapes; DynShape: any shape, read from KParams.
-template <int D_, int N_, int RP_>
-struct FixShape {
-    static constexpr int D = D_, N = N_, NK = (N_ + 15) / 16 * 16, MP = 2 * NK, RP = RP_;
-    static constexpr int NW = (N_ + 63) / 64 * 64, WPT = NW / 64, NSPLIT = stage1_splits(NK);
-    static constexpr bool kVariants = false;  // end-effector cost only (the reference's)
-    static constexpr bool kDense = false;
-    static constexpr int kNW = NW;             // lanes per trajectory (0: only known at run time)
-    // stage-1 k-quads per split-K unit when the split is even (else 0: checked per quad)
-    static constexpr int KQU = (NK / 16) % NSPLIT == 0 ? (NK / 16) / NSPLIT : 0;
-    __device__ explicit FixShape(const KParams&) {}
-};
-// The dense operator (--operator-rank -1: R = N, F = L = [K; dK], V_R = I, so G = y'' and z = e') of a
-// fixed shape, for k_lean's GD single loop: one split, every operator fragment streamed from L2.
-template <int D_, int N_>
-struct DenseShape {
-    static constexpr int D = D_, N = N_, NK = (N_ + 15) / 16 * 16, MP = 2 * NK, RP = NK;
-    static constexpr int NW = (N_ + 63) / 64 * 64, WPT = NW / 64, NSPLIT = 1;
-    static constexpr bool kVariants = false;
-    static constexpr bool kDense = true;
-    static constexpr int kNW = NW;
-    static constexpr int KQU = 0;
-    __device__ explicit DenseShape(const KParams&) {}
-};
-template <int D_>
-struct DynShape {
-    static constexpr int D = D_;
-    static constexpr bool kVariants = true;  // cost variants chosen at run time (whole_robot)
-    static constexpr bool kDense = false;
-    static constexpr int kNW = 0;
-    static constexpr int KQU = 0;
-    int N, NK, MP, RP, NW, WPT, NSPLIT;
-    __device__ explicit DynShape(const KParams& P)
-        : N(P.N), NK(P.NK), MP(P.MP), RP(P.RP), NW(P.NW), WPT(P.NW >> 6), NSPLIT(P.nsplit) {}
-};
-constexpr int kS1Q(int maxt) { return maxt <= 256 ? 8 : 4; }   // stage-1 float4 per wave
-constexpr int kS2T(int maxt) { return maxt <= 256 ? 8 : 2; }   // stage-2 tiles per wave (KQ2 ≤ 2)
-// MP of a shape-specialised shape (0 for DynShape, whose MP is a run-time value)
-template <class S>
-constexpr int shape_mp() {
-    if constexpr (S::kNW > 0) return S::MP;
-    else return 0;
-}
-
 // Row layout of the optimiser's [a; b] / [T; V] buffers and of F: the velocity
 // half starts at row NK (= N rounded up to 16), so the position half is whole
 // k-quads of its own and stage 1 can skip the velocity half when b is zero
@@ -1225,7 +263,7 @@ constexpr int shape_mp() {
 // batches outside k_lean's set.  Accepting a trial takes α_j and its [T; V] as they are.
 // When an inner loop ends (PH_RESYNC) [T; V] is replaced by eval_exact(α).
 // FULL (shape-specialised REGOPS launches of exactly MAXT threads): the stage-2 tiles per wave are
-// known exactly, so only those operator fragments occupy VGPRs (as in k_gd_single<…, FULL>).
+// known exactly, so only those operator fragments occupy VGPRs (as in k_lean<…, FULL>).
 template <class S, int MAXT, bool OPS_LDS, bool REGOPS, bool BLS, bool FULL = false>
 // 256-thread workgroups without register-resident operators fit two per CU (≤ 256 VGPRs); the
 // REGOPS variants need more and keep one (they are launched one per CU anyway).
@@ -1834,11 +872,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && !REGOPS) ? 2 : 1) void k_opti
         // ------------------------------------------------------- update
         float q2[D], v2[D], aj[BLS ? D : 1];
         // (K / dK rows per pipelined batch of the trial's exact evaluation: 8, as the resync's)
-#ifndef IRM_X_TRIAL_U
         constexpr int kTrialU = 8;
-#else
-        constexpr int kTrialU = IRM_X_TRIAL_U;
-#endif
         if constexpr (BLS) {
             // the trial's α_j = fl(fl(c_j·α) − fl(lr_j·ĝ)), ĝ = G/‖G‖ (optimizer_BLS.py:139, 165), through
             // X's position rows (consumed by this round's stage 1 and latch; rewritten by the gradient
@@ -2523,11 +1557,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     // so the per-round evaluation does not wait on its LDS reads
     // (and the 3-joint GD dual loop: C3 faithful 3.70 -> 3.60 ms; the BLS flow with it measured C3-BLS
     // −0.5 % but C2 +2.7 %, not used; the 7-DoF dual loop spills with it)
-#if defined(IRM_X_OREG_ALL)
-    constexpr bool OREG = true;
-#else
     constexpr bool OREG = GD1 || (D <= 3 && !BLS);
-#endif
     f32x4 oreg[OREG ? 6 : 1];
     const bool obs_reg = ((P.O + 3) >> 2) == 3;
 #pragma unroll
@@ -2942,13 +1972,11 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     // (its trial's own residual folded in, so the direction is the trial iterate's)
     // the GD single loop's G tiles issued after the stage-2 barrier (their MFMAs under the update and
     // evaluation; C3 -2.0 %, bit-identical)
-#ifdef IRM_X_GLATE_ALL
-    constexpr bool kGLate = !BLS && !DENSE && kS2Fix && kS2Batch;
-#else
+    // (the same in every non-BLS flow measured neutral on C4, C5, C7 and +1.2 % on the 3-joint GD dual loop,
+    // profiles/r05_glate_ab.txt: not kept)
     // (WPTL > 1 only: glate_tiles' waves write G rows of trajectories they do not own, and with one wave per
-    // trajectory — N ≤ 64 — only a wave barrier would sit between that write and the owner's read)
+    // trajectory — N ≤ 64 — only a wave barrier would sit between that write and the owner's read: a race)
     constexpr bool kGLate = GD1 && D <= 3 && kS2Fix && kS2Batch && WPTL > 1;
-#endif
     f32x4 glY0 = f32x4{0.f, 0.f, 0.f, 0.f}, glY1 = f32x4{0.f, 0.f, 0.f, 0.f};
     // (kGLate) the G tiles, issued right after the stage-2 barrier: their MFMAs under the update /
     // evaluation's VALU work; Gb is read after the evaluation's barrier (the decision).  Issued after the
@@ -3701,19 +2729,12 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     // spills there (C3 faithful 4.57 -> 4.42 ms, C3 BLS faithful 5.68 -> 5.60, C2 0.706 -> 0.689, same
     // box, same sums in the same order); the D = 7 / two-waypoint variants keep 2 (register peak)
     constexpr bool kReloadOps = D > 3 && MAXT > 256;
-#ifndef IRM_X_RESYNC_U
     constexpr int kResyncU = (D <= 3 && WPL == 1) ? 8 : 2;
-#else
-    constexpr int kResyncU = (D <= 3 && WPL == 1) ? IRM_X_RESYNC_U : 2;
-#endif
     // ---------------------------------------------------------- rounds
     // The second half of the waves (4-7: the younger partner on each SIMD) loses VALU arbitration to
     // the older one in every phase; static priority for that half (MI355X_MICROARCH.md, two waves per
     // SIMD, item 4): C3 +1.7 %.  Priority only reorders issue: results are unchanged.
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#ifdef IRM_X_PRIO_RESTORE
-    bool hm_prev = false;  // (kHelp) the previous round was a helper round: its priorities are still set
-#endif
     // ---- the all-live loop (C3's kernel, kTopC3).  A workgroup whose every slot holds a problem runs its
     // rounds here up to and including the first in which one of its trajectories stops (a rejected step, or
     // max_inner reached); the loop below takes over from there, and runs a ragged batch's last, partial
@@ -3948,15 +2969,8 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                 else __builtin_amdgcn_s_setprio(0);
             }
             // (the helper priorities stay set in the rounds after a helper round — a lone trajectory's resync
-            // rounds: t* keeps the issue lead there.  Restoring the launch's split once the helper rounds end,
-            // IRM_X_PRIO_RESTORE, measured C3-BLS faithful +0.8 %, C2 even; priority only reorders issue)
-#ifdef IRM_X_PRIO_RESTORE
-            else if (hm_prev) {  // back to the launch's split (waves 4-7 at 1)
-                if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-                else __builtin_amdgcn_s_setprio(0);
-            }
-            hm_prev = hm;
-#endif
+            // rounds: t* keeps the issue lead there.  Restoring the launch's split (waves 4-7 at 1) once the helper
+            // rounds end measured C3-BLS faithful +0.8 %, C2 even, and is not done; priority only reorders issue)
             // t* publishes its α, T, V for the helper at the top of each helper round (the helper reads them
             // after this round's G-tile barrier), instead of after every accepted trial of every trajectory
             if constexpr (kSSLazy) {
@@ -4178,11 +3192,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         // the GD single loop's G rows of the α update read with the direction (stage 2 wrote both), so their
         // LDS round trip is off the decision's path: C3 −1.3 %; the dual loop, C5 and C7 measured 0.8-1 %
         // slower with it (bit-identical either way)
-#ifdef IRM_X_GPRE
-        constexpr bool kGPre = !BLS;
-#else
         constexpr bool kGPre = GD1 && D <= 3 && !kGLate;
-#endif
         float Gp[kGPre ? WPL : 1][D];
         // BLS: this slot's trial iterate α_j read with the direction (bls_gz wrote it), off the accept's path
         constexpr bool kAjPre = BLS;
@@ -4674,42 +3684,6 @@ __global__ __launch_bounds__(MAXT) void k_forward(KParams P, int mode) {
 }
 
 // ------------------------------------------------------------- launchers
-template <class Fn>
-inline hipError_t dispatch_d(int D, Fn&& fn) {
-    switch (D) {
-        case 1: return fn(std::integral_constant<int, 1>{});
-        case 2: return fn(std::integral_constant<int, 2>{});
-        case 3: return fn(std::integral_constant<int, 3>{});
-        case 4: return fn(std::integral_constant<int, 4>{});
-        case 5: return fn(std::integral_constant<int, 5>{});
-        case 6: return fn(std::integral_constant<int, 6>{});
-        case 7: return fn(std::integral_constant<int, 7>{});
-        case 8: return fn(std::integral_constant<int, 8>{});
-        default: return hipErrorInvalidValue;
-    }
-}
-
-template <class Fn>
-inline hipError_t dispatch_t(int BT, Fn&& fn) {
-    if (BT <= 256) return fn(std::integral_constant<int, 256>{});
-    if (BT <= 512) return fn(std::integral_constant<int, 512>{});
-    if (BT <= 1024) return fn(std::integral_constant<int, 1024>{});
-    return hipErrorInvalidValue;
-}
-
-template <class K, class... Args>
-inline hipError_t launch_lds(K kernel, int grid, int threads, size_t lds, hipStream_t s, Args... args) {
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, s, args...);
-    return hipGetLastError();
-}
-
-template <class T>
-struct type_tag {
-    using type = T;
-};
-
 // LDS of k_lean: the optimiser head + obstacles, no staged F fragments, the lean regions.
 inline size_t lean_lds(const KParams& p, bool help = false, bool bls = false, bool dense = false) {
     KParams q = p;
@@ -4718,14 +3692,15 @@ inline size_t lean_lds(const KParams& p, bool help = false, bool bls = false, bo
                               p.D, help ? p.BT : 0, bls, dense).total * 4;
 }
 
-// The lean kernel's control flow for a launch (-1: the general kernel serves it): the GD single
-// loop (dualOptimization = max_outer_iteration > 1, optimizer_GD.py:18) without extended-vis
+// The optimiser's control flow in LeanFlow terms (k_optimize runs every flow in one instantiation): the GD
+// single loop (dualOptimization = max_outer_iteration > 1, optimizer_GD.py:18) without extended-vis
 // snapshots is the bench flow; GD with snapshots or a dual loop, and BLS, the full flows.
-inline int lean_flow(const KParams& p) {
-    if (!p.lean_ok) return -1;
+inline int optimizer_flow(const KParams& p) {
     if (p.optimizer == IRM_OPT_BLS) return LF_BLS;
     return (p.max_outer <= 1 && !p.record_series) ? LF_GD1 : LF_GD2;
 }
+// The lean kernel's control flow for a launch (-1: the general kernel serves it).
+inline int lean_flow(const KParams& p) { return p.lean_ok ? optimizer_flow(p) : -1; }
 // help: the launch's instantiation carries the BLS line-search helpers' exchange regions (lean_help), so
 // the check sees the LDS the launch will request (per-problem obstacle tables grow the base with TB·O)
 inline bool lean_fits(const KParams& p, bool help = false, bool bls = false) {
@@ -4744,10 +3719,24 @@ inline int shape_name(char* buf, size_t n) {
     else return snprintf(buf, n, "DynShape<%d>", Sh::D);
 }
 inline const char* flow_name(int flow) { return flow == LF_GD1 ? "GD1" : flow == LF_GD2 ? "GD2" : "BLS"; }
-// the optimiser's control flow in LeanFlow terms (k_optimize runs every flow in one instantiation)
-inline int optimizer_flow(const KParams& p) {
-    if (p.optimizer == IRM_OPT_BLS) return LF_BLS;
-    return (p.max_outer <= 1 && !p.record_series) ? LF_GD1 : LF_GD2;
+// What a k_lean launch records in `desc` besides run_optimizer's fields: the instantiation's name, its flow,
+// waypoints per lane and per-stage ranks (`queue`: the work queue's instantiation).
+template <class Sh>
+inline void describe_lean(LaunchDesc* desc, int tt, int wpl, bool full, int flow, bool queue) {
+    if (!desc) return;
+    char sn[48];
+    shape_name<Sh>(sn, sizeof(sn));
+    snprintf(desc->kernel, sizeof(desc->kernel), "k_lean<%s,%d,%d,%s,%s%s>", sn, tt, wpl, full ? "FULL" : "PART",
+             flow_name(flow), queue ? ",QUEUE" : "");
+    desc->lean = 1;
+    desc->flow = flow;
+    desc->wpl = wpl;
+    desc->rank_z = desc->rank_dir = 16;  // k_lean's per-stage ranks at RP = 32
+    desc->rank_g = 24;
+    if constexpr (Sh::kDense) {  // V_R = I: G is y'' and z is e' (no MFMAs), the direction at rank N
+        desc->rank_z = desc->rank_g = 0;
+        desc->rank_dir = Sh::RP;
+    }
 }
 
 // The one place an optimiser kernel is launched: records what runs in `desc` (irm_optimize_plan) and
@@ -4767,21 +3756,7 @@ inline hipError_t run_optimizer(LaunchDesc* desc, K kernel, int grid, int thread
 
 template <class Sh, int TT, int WPL, bool FULL, int FLOW>
 hipError_t launch_lean_one(const KParams& p, int grid, hipStream_t s, LaunchDesc* desc) {
-    if (desc) {
-        char sn[48];
-        shape_name<Sh>(sn, sizeof(sn));
-        snprintf(desc->kernel, sizeof(desc->kernel), "k_lean<%s,%d,%d,%s,%s>", sn, TT, WPL, FULL ? "FULL" : "PART",
-                 flow_name(FLOW));
-        desc->lean = 1;
-        desc->flow = FLOW;
-        desc->wpl = WPL;
-        desc->rank_z = desc->rank_dir = 16;  // k_lean's per-stage ranks at RP = 32
-        desc->rank_g = 24;
-        if constexpr (Sh::kDense) {  // V_R = I: G is y'' and z is e' (no MFMAs), the direction at rank N
-            desc->rank_z = desc->rank_g = 0;
-            desc->rank_dir = Sh::RP;
-        }
-    }
+    describe_lean<Sh>(desc, TT, WPL, FULL, FLOW, false);
     return run_optimizer(desc, k_lean<Sh, TT, WPL, FULL, FLOW>, grid, p.BT,
                          lean_lds(p, lean_help<Sh, TT, WPL, FULL, FLOW>(), FLOW == LF_BLS, Sh::kDense), s, p);
 }
@@ -4833,17 +3808,8 @@ hipError_t launch_lean_queue_flow(const KParams& p, int grid, hipStream_t s, Lau
     }
     if (G <= 0 || G >= grid || !p.queue) return hipSuccess;
     *served = true;
-    if (desc) {
-        char sn[48];
-        shape_name<Sh>(sn, sizeof(sn));
-        snprintf(desc->kernel, sizeof(desc->kernel), "k_lean<%s,%d,1,FULL,%s,QUEUE>", sn, TT, flow_name(FLOW));
-        desc->lean = 1;
-        desc->flow = FLOW;
-        desc->wpl = 1;
-        desc->rank_z = desc->rank_dir = 16;
-        desc->rank_g = 24;
-        desc->queue_groups = G;
-    }
+    describe_lean<Sh>(desc, TT, 1, true, FLOW, true);
+    if (desc) desc->queue_groups = G;
     if (!desc || !desc->describe_only) {
         const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)p.queue, G * p.TB, 1, s);
         if (e != hipSuccess) return e;
@@ -4990,15 +3956,5 @@ hipError_t launch_forward_dim(const KParams& p, int mode, hipStream_t s) {
         return launch_lds(k_forward<D, TT>, grid, p.BT, lds, s, p, mode);
     });
 }
-
-// Instantiated in irm_opt_inst.hip (IRM_INST_* macros); irm_kernels.hip only dispatches.
-#define IRM_FIX_SHAPES(X) X(3, 50) X(3, 64) X(3, 128) X(3, 256) X(7, 128) X(7, 256)
-#define IRM_EXTERN_FIX(D_, N_) \
-    extern template hipError_t launch_optimize_shape<FixShape<D_, N_, 32>>(const KParams&, hipStream_t, LaunchDesc*);
-#define IRM_EXTERN_DENSE(D_, N_) \
-    extern template hipError_t launch_dense_shape<DenseShape<D_, N_>>(const KParams&, hipStream_t, LaunchDesc*, bool*);
-#define IRM_EXTERN_DYN(D_)                                                                                      \
-    extern template hipError_t launch_optimize_shape<DynShape<D_>>(const KParams&, hipStream_t, LaunchDesc*); \
-    extern template hipError_t launch_forward_dim<D_>(const KParams&, int, hipStream_t);
 
 }  // namespace irm

@@ -1,7 +1,7 @@
 // irm_opt_inst.hip — one instantiation unit of the optimiser templates, compiled once per
 // shape by irm_motion_planning_amd/build.py (in parallel):
 //   -DIRM_INST_DYN=<D>                           k_optimize<DynShape<D>> + k_forward<D>
-//   -DIRM_INST_FIX_D=<D> -DIRM_INST_FIX_N=<N>      dispatch + lean k_gd_single<FixShape<D, N, 32>>
+//   -DIRM_INST_FIX_D=<D> -DIRM_INST_FIX_N=<N>      dispatch + lean k_lean<FixShape<D, N, 32>>
 //   -DIRM_INST_GEN_D=<D> -DIRM_INST_GEN_N=<N>      general k_optimize<FixShape<D, N, 32>>
 //   -DIRM_INST_DENSE_D=<D> -DIRM_INST_DENSE_N=<N>  k_lean<DenseShape<D, N>> (the dense operator's GD loop)
 //   -DIRM_INST_FIXQ_D=<D> -DIRM_INST_FIXQ_N=<N>    k_lean<FixShape<D, N, 32>, …, QUE> (the work queue's kernels)

@@ -1,6 +1,6 @@
 """Inputs, references and the fixture writer of the per-waypoint physics tests (tests/test_physics_host.py on
 the CPU, tests/test_gpu_physics.py on the device): sincos_poly / sincos_fast, the FK / Jacobian recurrences and
-the obstacle potential of irm_kernels_impl.hpp, away from the small angles and the obstacle counts the other
+the obstacle potential of irm_physics.hpp, away from the small angles and the obstacle counts the other
 suites feed.
 
 1. `SINCOS_C` restates sincos_poly in C operation for operation (the kernel's constants, fmaf where the kernel
@@ -38,7 +38,7 @@ SINCOS_C = r"""
 static inline float fb(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 static inline uint32_t bf(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 
-/* irm_kernels_impl.hpp, sincos_poly: the same operations in the same order */
+/* irm_physics.hpp, sincos_poly: the same operations in the same order */
 static void sincos_poly(float x, float* sn, float* cs) {
     const float t = fmaf(x, 0.636619772f, 12582912.0f);
     const float kf = t - 12582912.0f;

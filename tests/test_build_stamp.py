@@ -38,6 +38,16 @@ def sandbox(tmp_path, monkeypatch):
     return tmp_path
 
 
+def test_every_header_is_a_dependency():
+    """An edit to any csrc/*.hpp rebuilds the objects: none is missing from build.HEADERS."""
+    import glob
+    hpps = glob.glob(os.path.join(build.CSRC, "*.hpp"))
+    assert len(hpps) > 4  # the part headers of irm_kernels_impl.hpp are there
+    have = {os.path.normpath(h) for h in build.HEADERS}
+    assert all(os.path.normpath(h) in have for h in hpps)
+    assert os.path.normpath(os.path.join(build.HERE, "..", "include", "irm.h")) in have
+
+
 def test_stamp_written_after_link(sandbox, monkeypatch):
     monkeypatch.setattr(build, "HIPCC", _fake_hipcc(sandbox))
     out = build.build(variant="stamptest", jobs=4)

@@ -1,4 +1,4 @@
-"""The BLS step direction's quotient (irm_kernels_impl.hpp, div_rcp with rcp_rn_of): with r = RN(1/b),
+"""The BLS step direction's quotient (irm_opt_common.hpp, div_rcp with rcp_rn_of): with r = RN(1/b),
 q = RN(a·r) and RN(q + (a − q·b)·r) must be the IEEE quotient RN(a/b) — optimizer_BLS.py:165's
 ĝ = g / norm.  And r itself: one Newton step RN(y + y·RN(1 − b·y)) from either faithful rounding y of 1/b
 (v_rcp_f32 is faithful) must give RN(1/b) for every divisor mantissa but all-ones, where rcp_rn_of selects

@@ -1,4 +1,4 @@
-"""The per-waypoint physics of irm_kernels_impl.hpp on an MI355X, off the beaten path: sincos_poly / sincos_fast
+"""The per-waypoint physics of irm_physics.hpp on an MI355X, off the beaten path: sincos_poly / sincos_fast
 over every quadrant and beyond the 1e4 fallback threshold, the FK / Jacobian recurrences, and the obstacle
 potential's three forms at the obstacle counts where its blocks begin and end and on degenerate geometry.
 Inputs, references and the fixture: tests/physics_cases.py; tests/test_physics_host.py measures the C

@@ -1,4 +1,4 @@
-"""sincos_poly (irm_kernels_impl.hpp) on the CPU: its C restatement (tests/physics_cases.py, SINCOS_C; fmaf,
+"""sincos_poly (irm_physics.hpp) on the CPU: its C restatement (tests/physics_cases.py, SINCOS_C; fmaf,
 -ffp-contract=off) measured against double sin / cos, the committed bit-pattern fixture regenerated, two mutants
 of the restatement shown to miss the bounds, and the references and inputs of tests/test_gpu_physics.py checked
 where that needs no device.
