@@ -402,6 +402,59 @@ int irm_dense_check_moving_dev(irm_ctx* ctx, const float* alpha_dev, const float
 int irm_optimize_plan_moving(const irm_ctx* ctx, int32_t batch, int32_t n_obstacles, int32_t record_series,
                              irm_launch_plan* out);
 
+/* Clearance: the signed distance between the arm's links and disc obstacles on the evaluation times — does the
+ * arm touch anything, and by how much does it miss?  The obstacle potential is a cost at points (the end effector,
+ * or the joints with whole_robot_cost); a link is the segment between two joints and can pass over an obstacle
+ * that both of its joints clear.  For trajectory b, evaluation time i of the context's grid (irm_set_eval_times),
+ * link l = 0 … D−1 and obstacle o, everything in fp32 and in this order:
+ *   q        the position sample at t_eval[i], irm_eval_any's arithmetic and bits
+ *   c_l      = c_{l−1} + q_l                                  (c_0 = q_0), and the rounding of that addition kept:
+ *   τ_l      = τ_{l−1} + ((c_{l−1} − (c_l − b)) + (q_l − b)),  b = c_l − c_{l−1},  τ_0 = 0      (two-sum: the bracket
+ *              is exactly (c_{l−1} + q_l) − c_l, so c_l + τ_l is the angle sum to second order)
+ *   sn0, cs0 = the kernels' sincos of c_l (the polynomial of the obstacle potential's FK; sincosf above 1e4 rad)
+ *   sn, cs   = fmaf(τ_l, cs0, sn0), fmaf(−τ_l, sn0, cs0)      sin and cos of c_l + τ_l to first order in τ_l.  Without
+ *              it the fp32 prefix sum alone moves a joint of a 7-link arm by 1.3e-6 at angles of 13 rad
+ *   x_l      = fmaf(L_l, cs_l, x_{l−1}),  y_l = fmaf(L_l, sn_l, y_{l−1}),  p_{−1} = (0, 0): the joint positions, in
+ *              the order of the potential's FK (to the bit where every τ_l is 0)
+ *   link l   the segment from p_{l−1} to p_l, with direction e = (L_l·cs_l, L_l·sn_l) — one product each, not the
+ *              difference of two positions — and inverse squared length w_l = 1/(L_l·L_l), an IEEE division
+ *   obstacle the table entry, or on a moving launch fmaf(t_eval[i], w, p) per coordinate as irm_dense_check_moving
+ *   u        = o − p_{l−1}                                    per coordinate
+ *   s        = min(max(fmaf(u_y, e_y, u_x·e_x)·w_l, 0), 1)    the projection onto the segment, clamped
+ *   r        = (fmaf(−s, e_x, u_x), fmaf(−s, e_y, u_y))
+ *   d        = sqrt(fmaf(r_y, r_y, r_x·r_x))                  the IEEE (correctly rounded) square root
+ *   g        = (d − radius_o) − link_radius                   the signed clearance, in that order
+ * radius_o is 0 without a radius table; link_radius ≥ 0 is one scalar for the whole arm (a capsule per link).
+ * Sample i has c_i = min over (l, o) of g and collides iff c_i < 0 (g = 0, touching, does not); the report's
+ * minimum is min over i of c_i.  Ties go to the lexicographically lowest (i, l, o).  With no obstacles every c_i
+ * and the minimum are +INFINITY, every argmin is −1 and nothing collides.  link_out[l] is the minimum of g over
+ * the samples and obstacles for link l alone.  The verdict covers the M samples, not the time between them; the
+ * links are not checked against each other.
+ * obstacle_radius: O floats shared by the batch (obstacle_stride 0), else one table per problem at
+ * obstacle_stride/2 floats (an odd stride with a radius table is IRM_EINVAL).  obstacle_velocity: as
+ * irm_dense_check_moving; NULL and an all-zero table give the same bits.  IRM_EINVAL: no evaluation grid, a
+ * negative batch, n_obstacles outside [0, IRM_MAX_OBSTACLES], obstacles missing with n_obstacles > 0, a negative or
+ * non-finite link_radius and, on the host entry point (which sees the values), a negative or non-finite radius or
+ * a non-finite velocity.  batch = 0 is a no-op.  A problem's result does not depend on the rest of the batch.
+ * Additive symbols: IRM_ABI_VERSION stays 3 and no struct changes layout; no reference counterpart. */
+typedef struct irm_clearance_report {
+    float min_clearance;
+    int32_t argmin_time, argmin_link, argmin_obstacle; /* indices into t_eval, links, obstacles; -1 if n_obstacles = 0 */
+    int32_t n_colliding, first_colliding;              /* samples with c_i < 0; first index into t_eval or -1 */
+    int32_t collision_free;                            /* n_colliding == 0 */
+    int32_t pad_;
+} irm_clearance_report;
+/* report_out: B records.  clear_out B×M (c_i), link_out B×D, joints_out B×M×D×2 (x_l, y_l of every sample, the
+ * positions the distances were taken from): each nullable. */
+int irm_clearance(irm_ctx* ctx, const float* alpha, const float* obstacles, int32_t n_obstacles, int32_t obstacle_stride,
+                  const float* obstacle_velocity, const float* obstacle_radius, float link_radius, int32_t batch,
+                  irm_clearance_report* report_out, float* clear_out, float* link_out, float* joints_out);
+/* Same, device pointers, enqueue-only on `stream` (hipStream_t). */
+int irm_clearance_dev(irm_ctx* ctx, const float* alpha_dev, const float* obstacles_dev, int32_t n_obstacles,
+                      int32_t obstacle_stride, const float* obstacle_velocity_dev, const float* obstacle_radius_dev,
+                      float link_radius, int32_t batch, irm_clearance_report* report_dev, float* clear_dev,
+                      float* link_dev, float* joints_dev, void* stream);
+
 /* End-effector goals: plan to a Cartesian target.  A problem may carry goal_xy = (p_x, p_y); row N−1 of the
  * trajectory is then held to the target through the end-effector FK f (robot.py:29-36) and its 2×D Jacobian
  * J_ee (robot.py:75-87) instead of to the joint configuration `goal`.  Three places change, nothing else:

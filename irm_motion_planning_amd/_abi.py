@@ -8,6 +8,7 @@ the calls raise IrmError.
 import ctypes
 import os
 
+from . import clearance as _clearance  # irm_clearance_report's mirror
 from . import via as _via  # irm_via's mirror lives with the via-point value object
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -262,6 +263,17 @@ PROTOTYPES = {
     ),
     "irm_optimize_plan_moving": (
         ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(IrmLaunchPlan)]
+    ),
+    # clearance of the links against disc obstacles (velocity and radius tables nullable)
+    "irm_clearance": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, c_float_p, c_float_p, ctypes.c_float,
+         ctypes.c_int32, ctypes.POINTER(_clearance.IrmClearanceReport), c_float_p, c_float_p, c_float_p],
+    ),
+    "irm_clearance_dev": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, c_float_p, c_float_p, ctypes.c_float,
+         ctypes.c_int32, ctypes.POINTER(_clearance.IrmClearanceReport), c_float_p, c_float_p, c_float_p, ctypes.c_void_p],
     ),
     # end-effector goals: the _moving twins' arguments plus goal_xy (B×2; NULL: the existing call), and the IK seed
     "irm_eval_cost_task": (

@@ -7,9 +7,10 @@ includes: irm_wave / irm_prof / irm_physics / irm_opt_common /
 irm_dispatch / irm_launch_decl .hpp) are
 instantiated in one object per problem shape (csrc/irm_opt_inst.hip compiled
 with IRM_INST_*), so the objects build in parallel; the host-API kernels and dispatch
-(irm_kernels.hip), the C ABI (irm_host.cpp) and the device-free operator build
+(irm_kernels.hip), the kernels of their own units (irm_dense.hip, irm_clearance.hip, irm_fit.hip; irm_dense_sample.hpp is
+what the first two share), the C ABI (irm_host.cpp) and the device-free operator build
 behind irm_ctx_create (irm_operator.cpp: build_operators, fill_kparams,
-choose_shape; no HIP header) are three more objects.  irm_layout.hpp is what
+choose_shape; no HIP header) are the other objects.  irm_layout.hpp is what
 host and kernels share without a HIP type (KParams, fragment and LDS layouts),
 irm_kernels.hpp adds the launchers.  Every csrc/*.hpp is a dependency of every
 object (HEADERS).  The .so lands next to this file so that it travels with the repository snapshot to the
@@ -119,6 +120,8 @@ def _units():
           for d, n in QUEUE_SHAPES]
     # evaluation at arbitrary times (irm_eval_any, irm_dense_check): kernels and launchers of their own
     u += [("irm_dense", "irm_dense.hip", [])]
+    # link-against-disc clearance on the evaluation times (irm_clearance): a kernel and launcher of its own
+    u += [("irm_clearance", "irm_clearance.hip", [])]
     # fitting and re-timing (irm_fit_alpha, irm_transfer_alpha): kernels and launchers of their own
     u += [("irm_fit", "irm_fit.hip", [])]
     return u

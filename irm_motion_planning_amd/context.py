@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import IrmBatchDev, IrmDenseReport, IrmInfo, IrmLaunchPlan, IrmParams, IrmStats, check, load_library
+from .clearance import CLEARANCE_REPORT_FIELDS, IrmClearanceReport
 from .via import IrmVia, ViaPoints
 
 _fp = _abi.c_float_p
@@ -248,6 +249,54 @@ class Context:
             out["cost"] = cost[0] if single else cost
         return out
 
+    def clearance(self, alpha, obstacles, obstacle_velocity=None, obstacle_radius=None, link_radius=0.0,
+                  with_samples=False, with_links=False, with_joints=False):
+        """Signed clearance between the arm's links (segments between consecutive joints, each a capsule of
+        link_radius) and disc obstacles on the evaluation times (irm_clearance): a dict of arrays named as
+        irm_clearance_report's fields, plus `clearance` ((B×)M: every sample's minimum), `link_clearance` ((B×)D:
+        every link's own minimum) and `joints` ((B×)M×D×2: the joint positions of every sample) on request.
+        obstacles: (O, 2) shared, or (B, O, 2) one table per problem, like dense_check; obstacle_velocity the same
+        shape (sample i sees obstacle o at p + t_eval[i]·w); obstacle_radius: a scalar, (O,) or, with per-problem
+        tables, (B, O) — None: points."""
+        a, single = self._batch(alpha, (self.N, self.D))
+        B = a.shape[0]
+        obs = _f32(obstacles)
+        O = obs.shape[-2] if obs.size else 0
+        stride = 0
+        if obs.ndim == 3:
+            if obs.shape[0] != B or obs.shape[2] != 2:
+                raise ValueError(f"per-problem obstacles must be ({B}, O, 2), got {obs.shape}")
+            stride = 2 * O
+        elif obs.size and (obs.ndim != 2 or obs.shape[1] != 2):
+            raise ValueError(f"shared obstacles must be (O, 2), got {obs.shape}")
+        vel = None if obstacle_velocity is None else self._velocity(obstacle_velocity, obs)
+        rad = None
+        if obstacle_radius is not None and O > 0:
+            want = (B, O) if stride else (O,)
+            try:
+                rad = _f32(np.broadcast_to(_f32(obstacle_radius), want))
+            except ValueError:
+                raise ValueError(f"obstacle_radius must broadcast to {want}, got {np.shape(obstacle_radius)}") from None
+        M = max(int(self.lib.irm_eval_times(self._h, None)), 0)
+        rep = (IrmClearanceReport * B)()
+        clear = np.zeros((B, M), np.float32) if with_samples else None
+        link = np.zeros((B, self.D), np.float32) if with_links else None
+        joints = np.zeros((B, M, self.D, 2), np.float32) if with_joints else None
+        check(self.lib.irm_clearance(self._h, _ptr(a), _ptr(obs), O, stride, _ptr(vel), _ptr(rad), float(link_radius), B,
+                                     rep, _ptr(clear), _ptr(link), _ptr(joints)))
+        out = {}
+        recs = np.frombuffer(rep, dtype=np.dtype(
+            [(name, np.float32 if ctype is ctypes.c_float else np.int32) for name, ctype in IrmClearanceReport._fields_]))
+        for name in CLEARANCE_REPORT_FIELDS:
+            vals = recs[name].copy()
+            if name == "collision_free":
+                vals = vals.astype(bool)
+            out[name] = vals[0] if single else vals
+        for name, arr in (("clearance", clear), ("link_clearance", link), ("joints", joints)):
+            if arr is not None:
+                out[name] = arr[0] if single else arr
+        return out
+
     # ------------------------------------------------- fitting and re-timing
     def set_fit_ridge(self, ridge):
         """The ridge ρ of every later fit_alpha / transfer_alpha (irm_set_fit_ridge: rebuilds W = (K + ρI)⁻¹ and
@@ -292,6 +341,17 @@ class Context:
     def fit_alpha_dev(self, traj_dev, batch, alpha_dev, stream=0):
         """Enqueue irm_fit_alpha_dev with raw device addresses (e.g. torch data_ptr())."""
         check(self.lib.irm_fit_alpha_dev(self._h, _dev(traj_dev), int(batch), _dev(alpha_dev), ctypes.c_void_p(stream)))
+
+    def clearance_dev(self, alpha_dev, obstacles_dev, n_obstacles, obstacle_stride, batch, report_dev,
+                      obstacle_velocity_dev=0, obstacle_radius_dev=0, link_radius=0.0, clear_dev=0, link_dev=0,
+                      joints_dev=0, stream=0):
+        """Enqueue irm_clearance_dev with raw device addresses (e.g. torch data_ptr()); 0: that table or output is
+        absent.  report_dev: batch records of 32 bytes (irm_clearance_report)."""
+        rep = ctypes.cast(ctypes.c_void_p(int(report_dev)), ctypes.POINTER(IrmClearanceReport))
+        check(self.lib.irm_clearance_dev(self._h, _dev(alpha_dev), _dev(obstacles_dev), int(n_obstacles),
+                                         int(obstacle_stride), _dev(obstacle_velocity_dev), _dev(obstacle_radius_dev),
+                                         float(link_radius), int(batch), rep, _dev(clear_dev), _dev(link_dev),
+                                         _dev(joints_dev), ctypes.c_void_p(stream)))
 
     def ik_seed_dev(self, start_dev, goal_xy_dev, batch, q_dev, residual_dev=0, stream=0):
         """Enqueue irm_ik_seed_dev with raw device addresses; residual_dev 0: no residual output."""

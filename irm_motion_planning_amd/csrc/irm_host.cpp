@@ -1084,6 +1084,104 @@ int irm_dense_check_moving(irm_ctx* c, const float* alpha, const float* obstacle
     return dense_check_host(c, alpha, obstacles, O, obstacle_stride, B, report_out, cost_out, obstacle_velocity);
 }
 
+// ------------------------------------------------- clearance of the links against disc obstacles
+}  // extern "C"
+
+namespace {
+
+// what irm_clearance and irm_clearance_dev both refuse (fn: the entry point's name)
+int clearance_check(const char* fn, const irm_ctx* c, const float* alpha, const float* obstacles, int32_t O,
+                    int32_t obstacle_stride, const float* radius, float link_radius, int32_t B, const void* report) {
+    if (!c || !alpha || !report) return fail(IRM_EINVAL, "%s: null argument", fn);
+    if (c->t_eval.empty()) return fail(IRM_EINVAL, "%s: no evaluation times set (irm_set_eval_times)", fn);
+    if (B < 0) return fail(IRM_EINVAL, "%s: negative batch", fn);
+    if (O < 0 || O > IRM_MAX_OBSTACLES)
+        return fail(IRM_EINVAL, "%s: n_obstacles=%d outside [0, %d]", fn, O, IRM_MAX_OBSTACLES);
+    if (obstacle_stride != 0 && (obstacle_stride < 2 * O || obstacle_stride < 0))
+        return fail(IRM_EINVAL, "%s: obstacle_stride=%d must be 0 (shared) or >= 2*n_obstacles=%d", fn, obstacle_stride,
+                    2 * O);
+    if (O > 0 && !obstacles) return fail(IRM_EINVAL, "%s: obstacles pointer missing", fn);
+    if (radius && (obstacle_stride & 1))
+        return fail(IRM_EINVAL, "%s: obstacle_stride=%d is odd: the radius tables lie obstacle_stride/2 floats apart", fn,
+                    obstacle_stride);
+    if (!(link_radius >= 0.f) || !std::isfinite(link_radius))
+        return fail(IRM_EINVAL, "%s: link_radius must be finite and >= 0", fn);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int irm_clearance_dev(irm_ctx* c, const float* alpha, const float* obstacles, int32_t O, int32_t obstacle_stride,
+                      const float* vel, const float* radius, float link_radius, int32_t B, irm_clearance_report* report,
+                      float* clear, float* link, float* joints, void* stream) {
+    if (clearance_check("irm_clearance_dev", c, alpha, obstacles, O, obstacle_stride, radius, link_radius, B, report))
+        return IRM_EINVAL;
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    KParams kp = c->kp;
+    kp.B = B;
+    kp.O = O;
+    kp.obs_stride = obstacle_stride;
+    kp.alpha0 = alpha;
+    kp.obstacles = obstacles;
+    if (vel && O > 0) {  // sample i sees the table at t_eval[i]
+        kp.moving = 1;
+        kp.obs_vel = vel;
+        kp.tsup = c->d_teval;
+    }
+    HIP_TRY(irm::launch_clearance(kp, c->d_KqT, (int)c->t_eval.size(), O > 0 ? radius : nullptr, obstacle_stride / 2,
+                                  link_radius, report, clear, link, joints, (hipStream_t)stream));
+    return IRM_OK;
+}
+
+int irm_clearance(irm_ctx* c, const float* alpha, const float* obstacles, int32_t O, int32_t obstacle_stride,
+                  const float* vel, const float* radius, float link_radius, int32_t B, irm_clearance_report* report_out,
+                  float* clear_out, float* link_out, float* joints_out) {
+    if (clearance_check("irm_clearance", c, alpha, obstacles, O, obstacle_stride, radius, link_radius, B, report_out))
+        return IRM_EINVAL;
+    if (O == 0) vel = radius = nullptr;
+    const size_t nobs = obstacle_stride ? (size_t)B * obstacle_stride : (size_t)O * 2;
+    const size_t nrad = obstacle_stride ? (size_t)B * (obstacle_stride / 2) : (size_t)O;
+    if (vel && check_vel("irm_clearance", vel, nobs)) return IRM_EINVAL;
+    if (radius)  // (per-problem tables: the floats between a table's O radii and the next table are not read)
+        for (size_t b = 0; b < (obstacle_stride ? (size_t)B : 1); ++b)
+            for (int o = 0; o < O; ++o) {
+                const float r = radius[b * (size_t)(obstacle_stride / 2) + o];
+                if (!(r >= 0.f) || !std::isfinite(r))
+                    return fail(IRM_EINVAL, "irm_clearance: obstacle_radius[%zu] must be finite and >= 0",
+                                b * (size_t)(obstacle_stride / 2) + o);
+            }
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    const int N = c->N, D = c->D, M = (int)c->t_eval.size();
+    const size_t nd = (size_t)B * N * D, bm = (size_t)B * M;
+    Stage st{c};
+    const size_t o_a = st.take(nd * 4), o_o = st.take(std::max<size_t>(nobs, 1) * 4),
+                 o_w = st.take(std::max<size_t>(nobs, 1) * 4), o_rad = st.take(std::max<size_t>(nrad, 1) * 4),
+                 o_r = st.take((size_t)B * sizeof(irm_clearance_report)), o_c = st.take(bm * 4),
+                 o_l = st.take((size_t)B * D * 4), o_j = st.take(joints_out ? bm * D * 2 * 4 : 4);
+    if (ensure_io(c, st.off)) return IRM_ENOMEM;
+    char* d = st.base();
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d + o_a, alpha, nd * 4, hipMemcpyHostToDevice, s));
+    if (nobs && O > 0) HIP_TRY(hipMemcpyAsync(d + o_o, obstacles, nobs * 4, hipMemcpyHostToDevice, s));
+    if (vel) HIP_TRY(hipMemcpyAsync(d + o_w, vel, nobs * 4, hipMemcpyHostToDevice, s));
+    if (radius) HIP_TRY(hipMemcpyAsync(d + o_rad, radius, nrad * 4, hipMemcpyHostToDevice, s));
+    const int rc = irm_clearance_dev(c, (const float*)(d + o_a), (const float*)(d + o_o), O, obstacle_stride,
+                                     vel ? (const float*)(d + o_w) : nullptr, radius ? (const float*)(d + o_rad) : nullptr,
+                                     link_radius, B, (irm_clearance_report*)(d + o_r), clear_out ? (float*)(d + o_c) : nullptr,
+                                     link_out ? (float*)(d + o_l) : nullptr, joints_out ? (float*)(d + o_j) : nullptr, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(report_out, d + o_r, (size_t)B * sizeof(irm_clearance_report), hipMemcpyDeviceToHost, s));
+    if (clear_out) HIP_TRY(hipMemcpyAsync(clear_out, d + o_c, bm * 4, hipMemcpyDeviceToHost, s));
+    if (link_out) HIP_TRY(hipMemcpyAsync(link_out, d + o_l, (size_t)B * D * 4, hipMemcpyDeviceToHost, s));
+    if (joints_out) HIP_TRY(hipMemcpyAsync(joints_out, d + o_j, bm * D * 2 * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return IRM_OK;
+}
+
 // ------------------------------------------------- fitting and re-timing
 }  // extern "C"
 

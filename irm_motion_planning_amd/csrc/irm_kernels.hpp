@@ -27,6 +27,12 @@ hipError_t launch_ik_seed(const KParams& p, const float* start, const float* goa
 hipError_t launch_eval_any(const KParams& p, const float* mT, int M, float* out, hipStream_t s);
 hipError_t launch_dense_check(const KParams& p, const float* kqT, const float* dkqT, int M, irm_dense_report* rep,
                               float* cost, hipStream_t s);
+// irm_clearance.hip — link-against-disc clearance on the evaluation times (irm_clearance).  radius: the obstacle
+// radii on the device (nullable; radius_stride floats between the problems' tables, 0 shared); rep B, clear B×M,
+// link B×D, joints B×M×D×2 (the last three nullable); a moving launch reads p.obs_vel and p.tsup (the evaluation times).
+hipError_t launch_clearance(const KParams& p, const float* kqT, int M, const float* radius, int radius_stride,
+                            float link_radius, irm_clearance_report* rep, float* clear, float* link, float* joints,
+                            hipStream_t s);
 // irm_fit.hip — fitting and re-timing.  wT / tT: the fit / transfer operator on the device in fp64, transposed
 // ([source row m][waypoint n], n_src × N; W is N × N); kq0: the fp32 query row of the source grid at t0 (n_src);
 // p.B problems of p.N waypoints.  start_out nullable.

@@ -14,7 +14,9 @@ Additive flags (no reference counterpart): --batch-size, --seed,
 --goal-xy (an end-effector target instead of a goal configuration; the goal number of the
 "start goal position" line is then the Cartesian distance) and --via-joint / --via-xy (via-points:
 interior support rows held to joint or end-effector targets; one stdout line names the chosen rows
-and one reports the via distances).
+and one reports the via distances), --clearance (the signed clearance between the arm's links and the obstacles as
+discs on M samples: one stdout line, on the batched path a second one and a min_clearance column in the
+summary file) with --obstacle-radius and --link-radius.
 """
 import argparse
 import os
@@ -156,7 +158,27 @@ def build_parser():
     parser.add_argument('--via-xy', type=float, nargs=3, action='append', default=None, metavar=('T', 'X', 'Y'),
                         help="Via-point: at plan time T the end effector is held to (X, Y); it passes through "
                              "and does not stop; repeatable (default: absent)")
+    parser.add_argument('--clearance', type=_sample_count, default=0, metavar='M',
+                        help="After the report (and --dense-check), evaluate the result on linspace(0, 1, M) and print "
+                             "the smallest signed distance between the arm's links and the obstacles, taken as discs "
+                             "of --obstacle-radius, where it occurs and how many samples collide; honours "
+                             "--obstacle-velocity (default: 0 = off)")
+    parser.add_argument('--obstacle-radius', type=_radius, default=0.0, metavar='R',
+                        help="--clearance: the radius of every obstacle (default: 0 = points)")
+    parser.add_argument('--link-radius', type=_radius, default=0.0, metavar='R',
+                        help="--clearance: the arm's links as capsules of this radius (default: 0 = segments)")
     return parser
+
+
+def _radius(x):
+    """--obstacle-radius / --link-radius: a finite length ≥ 0."""
+    try:
+        r = float(x)
+    except ValueError:
+        r = -1.0
+    if not (0.0 <= r < float("inf")):
+        raise argparse.ArgumentTypeError(f"expected a radius >= 0, got {x!r}")
+    return r
 
 
 def _sample_count(x):
@@ -210,6 +232,30 @@ def dense_report(context, alpha, obstacles, M, obstacle_velocity=None):
           str(f32(first["min_position"])) + ";",
           "velocity limit", "ok" if first["velocity_ok"] else "exceeded", "with", f32(first["max_abs_velocity"]))
     np.savetxt(DENSE_RESULT, context.eval_any(alpha if alpha.ndim == 2 else alpha[0], 0))
+    return rep
+
+
+def clearance_report(context, alpha, obstacles, args, obstacle_velocity=None):
+    """--clearance M: the links' clearance on linspace(0, 1, M).  Prints problem 0's line and returns the batch's
+    report (Context.clearance; obstacle_velocity: the --obstacle-velocity table)."""
+    M = args.clearance
+    t = np.linspace(0, 1, M, dtype=np.float32)
+    context.set_eval_times(t)
+    alpha = np.asarray(alpha, np.float32)
+    rep = context.clearance(alpha, obstacles, obstacle_velocity=obstacle_velocity,
+                            obstacle_radius=args.obstacle_radius, link_radius=args.link_radius)
+    first = {k: (v if alpha.ndim == 2 else v[0]) for k, v in rep.items()}
+    if int(first["argmin_time"]) < 0:
+        where = "no obstacles"
+    else:
+        where = ("at t=" + str(t[int(first["argmin_time"])]) + " link " + str(int(first["argmin_link"])) + " obstacle " +
+                 str(int(first["argmin_obstacle"])))
+    if first["collision_free"]:
+        verdict = "collision-free"
+    else:
+        verdict = (str(int(first["n_colliding"])) + " colliding samples, the first at t=" +
+                   str(t[int(first["first_colliding"])]))
+    print(f"clearance ({M} samples): min", np.float32(first["min_clearance"]), where + ";", verdict)
     return rep
 
 
@@ -313,7 +359,13 @@ def run_batch(optimizer, args):
               "the waypoints")
     batch_io.write_result(batch_io.RESULT, traj[0])
     batch_io.write_result_batch(batch_io.RESULT_BATCH, traj)
-    batch_io.write_summary(batch_io.SUMMARY_BATCH, avg, mx, ok, stats)
+    min_clearance = None
+    if getattr(args, "clearance", 0) > 0:
+        rep = clearance_report(optimizer.context, alpha, env.obstacles, args, optimizer.obstacle_velocity)
+        print("clearance:", int(np.sum(np.asarray(ok, bool) & ~rep["collision_free"])), "of", int(np.sum(ok)),
+              "problems that fulfil the constraints on the support grid collide")
+        min_clearance = rep["min_clearance"]
+    batch_io.write_summary(batch_io.SUMMARY_BATCH, avg, mx, ok, stats, min_clearance=min_clearance)
     if series is not None:
         lens = stats["series_len"]
         frames0 = series[0][: int(lens[0])]
@@ -400,6 +452,8 @@ def main(argv=None):
     np.savetxt("trajectory_result.txt", np_trajectory)
     if args.dense_check > 0:
         dense_report(optimizer.context, result_alpha, env.obstacles, args.dense_check, optimizer.obstacle_velocity)
+    if args.clearance > 0:
+        clearance_report(optimizer.context, result_alpha, env.obstacles, args, optimizer.obstacle_velocity)
     if args.extended_vis:
         p_np = np.array(p)
         print(p_np.shape)

@@ -2,8 +2,9 @@
 code (the .hip sources) to gfx950 assembly with that unit's own flags (hipcc --cuda-device-only -S), once
 from each tree's csrc/ (the unit's name as its compilation-unit id, so that the trees' paths do not enter),
 drops the .ident line and compares the two files byte for byte.  One line per unit:
-`identical`, or the first differing line; exit status 1 on any difference.  The check for a change that
-only moves or tidies kernel source (profiles/header_split_isa.txt).
+`identical`, or the first differing line; exit status 1 on any difference.  A unit whose source only one of the
+trees has (a unit the change adds) is named as such and is no difference.  The check for a change that
+only moves or tidies kernel source (profiles/header_split_isa.txt, profiles/dense_sample_split_isa.txt).
 
     python tools/isa_same.py TREE_A TREE_B [--extra "FLAGS"] [-j 8]
 
@@ -41,6 +42,10 @@ def asm(tree, tag, unit):
 
 
 def one(unit):
+    have = [os.path.exists(os.path.join(t, "irm_motion_planning_amd", "csrc", unit[1])) for t in trees]
+    if not all(have):
+        where = f"only in {trees[have.index(True)]}" if any(have) else "in neither tree"
+        return f"{unit[0]}: {unit[1]} {where}"
     a, b = asm(trees[0], "a", unit), asm(trees[1], "b", unit)
     if a == b:
         return f"{unit[0]}: identical ({len(a)} lines)"
