@@ -160,186 +160,80 @@ class IrmDenseReport(ctypes.Structure):
 DENSE_REPORT_FIELDS = [f[0] for f in IrmDenseReport._fields_ if f[0] != "pad_"]
 
 
+def _variants(base, args, moving=None, task=None, via=None, last=()):
+    """The rows of one family: `base` and its _moving, _task and _via twins (each given as the argument types it
+    appends to the twin before it; None: the family has no such twin), every one followed by `last` (the _dev
+    forms: the stream).  `base` "a_dev" names its twins a_moving_dev, …"""
+    stem, dev = (base[:-4], "_dev") if base.endswith("_dev") else (base, "")
+    rows, args = {base: (ctypes.c_int, list(args) + list(last))}, list(args)
+    for suffix, extra in (("_moving", moving), ("_task", task), ("_via", via)):
+        if extra is not None:
+            args = args + list(extra)
+            rows[stem + suffix + dev] = (ctypes.c_int, args + list(last))
+    return rows
+
+
+_i32, _f, _h = ctypes.c_int32, ctypes.c_float, ctypes.c_void_p
+_via_p = ctypes.POINTER(_via.IrmVia)
+_COST = [_h, c_float_p, c_float_p, c_float_p, c_float_p, _i32, _i32, _f, _f, _f, c_float_p]
+_OPTIMIZE = [_h, c_float_p, c_float_p, c_float_p, c_float_p, _i32, _i32, _i32, c_float_p, c_float_p,
+             ctypes.POINTER(IrmStats), c_float_p]
+_DENSE = [_h, c_float_p, c_float_p, _i32, _i32, _i32, ctypes.POINTER(IrmDenseReport), c_float_p]
+_PLAN = [_h, _i32, _i32, _i32, ctypes.POINTER(IrmLaunchPlan)]
+_CLEARANCE = [_h, c_float_p, c_float_p, _i32, _i32, c_float_p, c_float_p, _f, _i32,
+              ctypes.POINTER(_clearance.IrmClearanceReport), c_float_p, c_float_p, c_float_p]
+
 # name -> (restype, argtypes); every symbol include/irm.h declares.
 PROTOTYPES = {
     "irm_params_default": (None, [ctypes.POINTER(IrmParams)]),
-    "irm_default_jac": (ctypes.c_int, [ctypes.c_int32, ctypes.c_float, ctypes.c_uint32, c_float_p]),
-    "irm_ctx_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(IrmParams)]),
-    "irm_ctx_destroy": (None, [ctypes.c_void_p]),
+    "irm_default_jac": (ctypes.c_int, [_i32, _f, ctypes.c_uint32, c_float_p]),
+    "irm_ctx_create": (ctypes.c_int, [ctypes.POINTER(_h), ctypes.POINTER(IrmParams)]),
+    "irm_ctx_destroy": (None, [_h]),
     "irm_last_error": (ctypes.c_char_p, []),
-    "irm_get_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IrmInfo)]),
-    "irm_kernel_matrices": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p]),
-    "irm_init_alpha": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, c_float_p]),
-    "irm_evaluate": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32, ctypes.c_int32, c_float_p]),
-    "irm_eval_cost": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
-         ctypes.c_float, ctypes.c_float, ctypes.c_float, c_float_p],
-    ),
-    "irm_eval_cost_grad": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
-         ctypes.c_float, ctypes.c_float, ctypes.c_float, c_float_p, c_float_p],
-    ),
-    "irm_constraints": (
-        ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, c_uint8_p, c_float_p]
-    ),
-    "irm_fk": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32, c_float_p, c_float_p]),
-    "irm_fk_joints": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32, c_float_p]),
-    "irm_compute_cost_vg": (
-        ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, c_float_p, c_float_p]
-    ),
-    "irm_optimize_batch": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
-         ctypes.c_int32, c_float_p, c_float_p, ctypes.POINTER(IrmStats), c_float_p],
-    ),
-    "irm_optimize_batch_dev": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IrmBatchDev), ctypes.c_void_p]),
-    "irm_series_capacity": (ctypes.c_int32, [ctypes.c_void_p]),
-    "irm_optimize_plan": (
-        ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(IrmLaunchPlan)]
-    ),
-    "irm_set_work_queue": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
-    "irm_work_queue_groups": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    "irm_query_matrices": (
-        ctypes.c_int, [ctypes.c_int32, ctypes.c_float, c_float_p, ctypes.c_int32, c_float_p, c_float_p]
-    ),
-    "irm_set_eval_times": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32]),
-    "irm_eval_times": (ctypes.c_int32, [ctypes.c_void_p, c_float_p]),
-    "irm_eval_any": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32, ctypes.c_int32, c_float_p]),
-    "irm_dense_check": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-         ctypes.POINTER(IrmDenseReport), c_float_p],
-    ),
-    "irm_dense_check_dev": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-         ctypes.POINTER(IrmDenseReport), c_float_p, ctypes.c_void_p],
-    ),
-    "irm_fit_operator": (
-        ctypes.c_int,
-        [ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_int32, ctypes.c_float, ctypes.c_float,
-         ctypes.c_float, c_double_p],
-    ),
-    "irm_set_fit_ridge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float]),
-    "irm_fit_alpha": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32, c_float_p]),
-    "irm_set_transfer": (
-        ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float]
-    ),
-    "irm_transfer_alpha": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32, c_float_p, c_float_p]),
-    "irm_fit_alpha_dev": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32, c_float_p, ctypes.c_void_p]),
-    "irm_transfer_alpha_dev": (
-        ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32, c_float_p, c_float_p, ctypes.c_void_p]
-    ),
-    # moving obstacles: the static twins' arguments plus the velocity table (NULL: the static call)
-    "irm_eval_cost_moving": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
-         ctypes.c_float, ctypes.c_float, ctypes.c_float, c_float_p, c_float_p],
-    ),
-    "irm_eval_cost_grad_moving": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
-         ctypes.c_float, ctypes.c_float, ctypes.c_float, c_float_p, c_float_p, c_float_p],
-    ),
-    "irm_optimize_batch_moving": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
-         ctypes.c_int32, c_float_p, c_float_p, ctypes.POINTER(IrmStats), c_float_p, c_float_p],
-    ),
-    "irm_optimize_batch_moving_dev": (
-        ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IrmBatchDev), c_float_p, ctypes.c_void_p]
-    ),
-    "irm_dense_check_moving": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-         ctypes.POINTER(IrmDenseReport), c_float_p, c_float_p],
-    ),
-    "irm_dense_check_moving_dev": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-         ctypes.POINTER(IrmDenseReport), c_float_p, c_float_p, ctypes.c_void_p],
-    ),
-    "irm_optimize_plan_moving": (
-        ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(IrmLaunchPlan)]
-    ),
+    "irm_get_info": (ctypes.c_int, [_h, ctypes.POINTER(IrmInfo)]),
+    "irm_kernel_matrices": (ctypes.c_int, [_h, c_float_p, c_float_p, c_float_p, c_float_p]),
+    "irm_init_alpha": (ctypes.c_int, [_h, c_float_p, c_float_p, _i32, c_float_p]),
+    "irm_evaluate": (ctypes.c_int, [_h, c_float_p, _i32, _i32, c_float_p]),
+    "irm_fk": (ctypes.c_int, [_h, c_float_p, _i32, c_float_p, c_float_p]),
+    "irm_fk_joints": (ctypes.c_int, [_h, c_float_p, _i32, c_float_p]),
+    "irm_compute_cost_vg": (ctypes.c_int, [_h, c_float_p, c_float_p, _i32, _i32, c_float_p, c_float_p]),
+    "irm_series_capacity": (_i32, [_h]),
+    "irm_set_work_queue": (ctypes.c_int, [_h, _i32]),
+    "irm_work_queue_groups": (ctypes.c_int, [_h, _i32, _i32, _i32]),
+    "irm_query_matrices": (ctypes.c_int, [_i32, _f, c_float_p, _i32, c_float_p, c_float_p]),
+    "irm_set_eval_times": (ctypes.c_int, [_h, c_float_p, _i32]),
+    "irm_eval_times": (_i32, [_h, c_float_p]),
+    "irm_eval_any": (ctypes.c_int, [_h, c_float_p, _i32, _i32, c_float_p]),
+    "irm_fit_operator": (ctypes.c_int, [_i32, _f, _f, _i32, _f, _f, _f, c_double_p]),
+    "irm_set_fit_ridge": (ctypes.c_int, [_h, _f]),
+    "irm_fit_alpha": (ctypes.c_int, [_h, c_float_p, _i32, c_float_p]),
+    "irm_set_transfer": (ctypes.c_int, [_h, _i32, _f, _f, _f]),
+    "irm_transfer_alpha": (ctypes.c_int, [_h, c_float_p, _i32, c_float_p, c_float_p]),
+    "irm_fit_alpha_dev": (ctypes.c_int, [_h, c_float_p, _i32, c_float_p, _h]),
+    "irm_transfer_alpha_dev": (ctypes.c_int, [_h, c_float_p, _i32, c_float_p, c_float_p, _h]),
+    # Moving obstacles, end-effector goals and via-points: each twin takes the arguments of the one before it and
+    # appends its own — the velocity table, goal_xy (B×2), an irm_via* — every one NULL for the existing call.
+    # irm_constraints has no velocity and its _via form a distance output; the _dev forms end in the stream
+    # (the via form: before the irm_via*); the launch plans differ only in name, but for the irm_via*.
+    **_variants("irm_eval_cost", _COST, [c_float_p], [c_float_p], [_via_p]),
+    **_variants("irm_eval_cost_grad", _COST + [c_float_p], [c_float_p], [c_float_p], [_via_p]),
+    **_variants("irm_constraints", [_h, c_float_p, c_float_p, c_float_p, _i32, c_uint8_p, c_float_p],
+                task=[c_float_p], via=[_via_p, c_float_p]),
+    **_variants("irm_optimize_batch", _OPTIMIZE, [c_float_p], [c_float_p], [_via_p]),
+    **_variants("irm_optimize_batch_dev", [_h, ctypes.POINTER(IrmBatchDev)], [c_float_p], [c_float_p], last=[_h]),
+    "irm_optimize_batch_via_dev": (ctypes.c_int, [_h, ctypes.POINTER(IrmBatchDev), c_float_p, c_float_p, _h, _via_p]),
+    **_variants("irm_optimize_plan", _PLAN, [], [], [_via_p]),
+    **_variants("irm_dense_check", _DENSE, [c_float_p]),
+    **_variants("irm_dense_check_dev", _DENSE, [c_float_p], last=[_h]),
     # clearance of the links against disc obstacles (velocity and radius tables nullable)
-    "irm_clearance": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, c_float_p, c_float_p, ctypes.c_float,
-         ctypes.c_int32, ctypes.POINTER(_clearance.IrmClearanceReport), c_float_p, c_float_p, c_float_p],
-    ),
-    "irm_clearance_dev": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32, c_float_p, c_float_p, ctypes.c_float,
-         ctypes.c_int32, ctypes.POINTER(_clearance.IrmClearanceReport), c_float_p, c_float_p, c_float_p, ctypes.c_void_p],
-    ),
-    # end-effector goals: the _moving twins' arguments plus goal_xy (B×2; NULL: the existing call), and the IK seed
-    "irm_eval_cost_task": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
-         ctypes.c_float, ctypes.c_float, ctypes.c_float, c_float_p, c_float_p, c_float_p],
-    ),
-    "irm_eval_cost_grad_task": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
-         ctypes.c_float, ctypes.c_float, ctypes.c_float, c_float_p, c_float_p, c_float_p, c_float_p],
-    ),
-    "irm_constraints_task": (
-        ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, c_uint8_p, c_float_p, c_float_p]
-    ),
-    "irm_optimize_batch_task": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
-         ctypes.c_int32, c_float_p, c_float_p, ctypes.POINTER(IrmStats), c_float_p, c_float_p, c_float_p],
-    ),
-    "irm_optimize_batch_task_dev": (
-        ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IrmBatchDev), c_float_p, c_float_p, ctypes.c_void_p]
-    ),
-    "irm_optimize_plan_task": (
-        ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(IrmLaunchPlan)]
-    ),
-    "irm_ik_seed": (ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, c_float_p, c_float_p]),
-    "irm_ik_seed_dev": (
-        ctypes.c_int, [ctypes.c_void_p, c_float_p, c_float_p, ctypes.c_int32, c_float_p, c_float_p, ctypes.c_void_p]
-    ),
-    # via-points: the _task twins' arguments plus a trailing irm_via* (NULL: the existing call)
-    "irm_eval_cost_via": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
-         ctypes.c_float, ctypes.c_float, ctypes.c_float, c_float_p, c_float_p, c_float_p, ctypes.POINTER(_via.IrmVia)],
-    ),
-    "irm_eval_cost_grad_via": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
-         ctypes.c_float, ctypes.c_float, ctypes.c_float, c_float_p, c_float_p, c_float_p, c_float_p,
-         ctypes.POINTER(_via.IrmVia)],
-    ),
-    "irm_constraints_via": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, c_uint8_p, c_float_p, c_float_p,
-         ctypes.POINTER(_via.IrmVia), c_float_p],
-    ),
-    "irm_optimize_batch_via": (
-        ctypes.c_int,
-        [ctypes.c_void_p, c_float_p, c_float_p, c_float_p, c_float_p, ctypes.c_int32, ctypes.c_int32,
-         ctypes.c_int32, c_float_p, c_float_p, ctypes.POINTER(IrmStats), c_float_p, c_float_p, c_float_p,
-         ctypes.POINTER(_via.IrmVia)],
-    ),
-    "irm_optimize_batch_via_dev": (
-        ctypes.c_int,
-        [ctypes.c_void_p, ctypes.POINTER(IrmBatchDev), c_float_p, c_float_p, ctypes.c_void_p, ctypes.POINTER(_via.IrmVia)],
-    ),
-    "irm_optimize_plan_via": (
-        ctypes.c_int,
-        [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(IrmLaunchPlan),
-         ctypes.POINTER(_via.IrmVia)],
-    ),
+    "irm_clearance": (ctypes.c_int, _CLEARANCE),
+    "irm_clearance_dev": (ctypes.c_int, _CLEARANCE + [_h]),
+    "irm_ik_seed": (ctypes.c_int, [_h, c_float_p, c_float_p, _i32, c_float_p, c_float_p]),
+    "irm_ik_seed_dev": (ctypes.c_int, [_h, c_float_p, c_float_p, _i32, c_float_p, c_float_p, _h]),
     "irm_build_id": (ctypes.c_char_p, []),
-    "irm_debug_phase_profile": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
-    "irm_debug_bls_trace_enable": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32]),
-    "irm_debug_bls_trace": (ctypes.c_int, [ctypes.c_void_p, c_float_p, ctypes.c_int32]),
+    "irm_debug_phase_profile": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_uint64), _i32]),
+    "irm_debug_bls_trace_enable": (ctypes.c_int, [_h, _i32]),
+    "irm_debug_bls_trace": (ctypes.c_int, [_h, c_float_p, _i32]),
 }
 
 _LIB = None

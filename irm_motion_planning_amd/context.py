@@ -30,6 +30,39 @@ def _dev(addr):
     return ctypes.cast(ctypes.c_void_p(int(addr) if addr else None), _fp)
 
 
+_SUFFIX = ("", "_moving", "_task", "_via")  # an entry point's twins, each the one before it plus one trailing argument
+
+
+def _rank(has_velocity, has_goal_xy, has_via):
+    """Which twin a call reaches (an index into _SUFFIX): via-points select _via, else an end-effector goal _task,
+    else a velocity table _moving, else the entry point itself."""
+    return 3 if has_via else 2 if has_goal_xy else 1 if has_velocity else 0
+
+
+def _via_struct(via, target):
+    """The irm_via of a ViaPoints' rows and kinds; target: the address of the targets (B×V×D fp32), None: NULL."""
+    v = IrmVia()
+    v.n_via = len(via)
+    for i, (r, c) in enumerate(zip(via.rows, via.cartesian)):
+        v.row[i], v.cartesian[i] = r, c
+    v.target = target
+    return v
+
+
+def _report(rep, fields, as_bool, single):
+    """An array of report structs (float / int32 fields) as a dict of arrays, one per name of `fields`; those of
+    `as_bool` as bool."""
+    recs = np.frombuffer(rep, dtype=np.dtype(
+        [(name, np.float32 if ctype is ctypes.c_float else np.int32) for name, ctype in rep._type_._fields_]))
+    out = {}
+    for name in fields:
+        vals = recs[name].copy()
+        if name in as_bool:
+            vals = vals.astype(bool)
+        out[name] = vals[0] if single else vals
+    return out
+
+
 def fit_operator(n_timesteps, rbf_variance=0.1, ridge=_abi.IRM_FIT_RIDGE_DEFAULT, n_src=0, rbf_variance_src=None,
                  t0=0.0, t1=1.0):
     """The fp64 operators of fit_alpha / transfer_alpha as the library builds them (irm_fit_operator; host only, no
@@ -124,19 +157,13 @@ class Context:
         runs the same kernel with a second obstacle table in LDS (a larger lds_bytes, possibly a smaller
         traj_per_block)."""
         pl = IrmLaunchPlan()
-        fn = self.lib.irm_optimize_plan if obstacle_velocity is None else self.lib.irm_optimize_plan_moving
-        if goal_xy is not None:
-            fn = self.lib.irm_optimize_plan_task
-        if via is not None and len(via):
+        n = _rank(obstacle_velocity is not None, goal_xy is not None, via is not None and len(via))
+        tail = ()
+        if n == 3:
             via.check_rows(self.N)
-            v = IrmVia()
-            v.n_via = len(via)
-            for i, (r, c) in enumerate(zip(via.rows, via.cartesian)):
-                v.row[i], v.cartesian[i] = r, c
-            check(self.lib.irm_optimize_plan_via(self._h, int(batch), int(n_obstacles), int(bool(series)),
-                                                 ctypes.byref(pl), ctypes.byref(v)))
-        else:
-            check(fn(self._h, int(batch), int(n_obstacles), int(bool(series)), ctypes.byref(pl)))
+            tail = (ctypes.byref(_via_struct(via, None)),)
+        check(getattr(self.lib, "irm_optimize_plan" + _SUFFIX[n])(self._h, int(batch), int(n_obstacles),
+                                                                  int(bool(series)), ctypes.byref(pl), *tail))
         d = {name: getattr(pl, name) for name, _ in IrmLaunchPlan._fields_}
         d["kernel"] = d["kernel"].decode()
         return d
@@ -220,31 +247,14 @@ class Context:
         (irm_dense_check_moving)."""
         a, single = self._batch(alpha, (self.N, self.D))
         B = a.shape[0]
-        obs = _f32(obstacles)
-        O = obs.shape[-2] if obs.size else 0
-        stride = 0
-        if obs.ndim == 3:
-            if obs.shape[0] != B or obs.shape[2] != 2:
-                raise ValueError(f"per-problem obstacles must be ({B}, O, 2), got {obs.shape}")
-            stride = 2 * O
-        elif obs.size and (obs.ndim != 2 or obs.shape[1] != 2):
-            raise ValueError(f"shared obstacles must be (O, 2), got {obs.shape}")
+        obs, O, stride = self._obstacle_table(obstacles, B)
         M = int(self.lib.irm_eval_times(self._h, None))
         rep = (IrmDenseReport * B)()
         cost = np.zeros((B, max(M, 0)), np.float32) if with_cost else None
-        if obstacle_velocity is None:
-            check(self.lib.irm_dense_check(self._h, _ptr(a), _ptr(obs), O, stride, B, rep, _ptr(cost)))
-        else:
-            vel = self._velocity(obstacle_velocity, obs)
-            check(self.lib.irm_dense_check_moving(self._h, _ptr(a), _ptr(obs), O, stride, B, rep, _ptr(cost), _ptr(vel)))
-        out = {}
-        recs = np.frombuffer(rep, dtype=np.dtype(
-            [(name, np.float32 if ctype is ctypes.c_float else np.int32) for name, ctype in IrmDenseReport._fields_]))
-        for name in _abi.DENSE_REPORT_FIELDS:
-            vals = recs[name].copy()
-            if name.endswith("_ok"):
-                vals = vals.astype(bool)
-            out[name] = vals[0] if single else vals
+        suffix, tail, _keep = self._variant(obstacle_velocity, None, None, obs, B)
+        check(getattr(self.lib, "irm_dense_check" + suffix)(self._h, _ptr(a), _ptr(obs), O, stride, B, rep, _ptr(cost),
+                                                            *tail))
+        out = _report(rep, _abi.DENSE_REPORT_FIELDS, ("position_ok", "velocity_ok"), single)
         if with_cost:
             out["cost"] = cost[0] if single else cost
         return out
@@ -260,15 +270,7 @@ class Context:
         tables, (B, O) — None: points."""
         a, single = self._batch(alpha, (self.N, self.D))
         B = a.shape[0]
-        obs = _f32(obstacles)
-        O = obs.shape[-2] if obs.size else 0
-        stride = 0
-        if obs.ndim == 3:
-            if obs.shape[0] != B or obs.shape[2] != 2:
-                raise ValueError(f"per-problem obstacles must be ({B}, O, 2), got {obs.shape}")
-            stride = 2 * O
-        elif obs.size and (obs.ndim != 2 or obs.shape[1] != 2):
-            raise ValueError(f"shared obstacles must be (O, 2), got {obs.shape}")
+        obs, O, stride = self._obstacle_table(obstacles, B)
         vel = None if obstacle_velocity is None else self._velocity(obstacle_velocity, obs)
         rad = None
         if obstacle_radius is not None and O > 0:
@@ -284,14 +286,7 @@ class Context:
         joints = np.zeros((B, M, self.D, 2), np.float32) if with_joints else None
         check(self.lib.irm_clearance(self._h, _ptr(a), _ptr(obs), O, stride, _ptr(vel), _ptr(rad), float(link_radius), B,
                                      rep, _ptr(clear), _ptr(link), _ptr(joints)))
-        out = {}
-        recs = np.frombuffer(rep, dtype=np.dtype(
-            [(name, np.float32 if ctype is ctypes.c_float else np.int32) for name, ctype in IrmClearanceReport._fields_]))
-        for name in CLEARANCE_REPORT_FIELDS:
-            vals = recs[name].copy()
-            if name == "collision_free":
-                vals = vals.astype(bool)
-            out[name] = vals[0] if single else vals
+        out = _report(rep, CLEARANCE_REPORT_FIELDS, ("collision_free",), single)
         for name, arr in (("clearance", clear), ("link_clearance", link), ("joints", joints)):
             if arr is not None:
                 out[name] = arr[0] if single else arr
@@ -380,20 +375,44 @@ class Context:
         """The end-effector targets of a task call: fp32 B×2 (one target broadcasts over the batch)."""
         return _f32(np.broadcast_to(_f32(goal_xy), (B, 2)))
 
-    def _via(self, via, B):
-        """The irm_via of a call (and the target array it points into, to be kept alive for the call): None for
-        via=None or an empty ViaPoints — the existing call."""
+    @staticmethod
+    def _obstacle_table(obstacles, B):
+        """(obs, O, stride) of an obstacle table: fp32 (O, 2) shared by the B problems (stride 0) or (B, O, 2) one
+        table per problem (stride 2·O floats); an empty table is O = 0."""
+        obs = _f32(obstacles)
+        O = obs.shape[-2] if obs.size else 0
+        stride = 0
+        if obs.ndim == 3:
+            if obs.shape[0] != B or obs.shape[2] != 2:
+                raise ValueError(f"per-problem obstacles must be ({B}, O, 2), got {obs.shape}")
+            stride = 2 * O
+        elif obs.size and (obs.ndim != 2 or obs.shape[1] != 2):
+            raise ValueError(f"shared obstacles must be (O, 2), got {obs.shape}")
+        return obs, O, stride
+
+    @staticmethod
+    def _has_via(via):
+        """Does a call hold via-points?  None and an empty ViaPoints do not — the existing call."""
         if via is None or len(via) == 0:
-            return None, None
+            return False
         if not isinstance(via, ViaPoints):
             raise TypeError(f"via must be a ViaPoints, got {type(via).__name__}")
-        tg = via.padded(B, self.D)
-        v = IrmVia()
-        v.n_via = len(via)
-        for i, (r, c) in enumerate(zip(via.rows, via.cartesian)):
-            v.row[i], v.cartesian[i] = r, c
-        v.target = tg.ctypes.data
-        return v, tg
+        return True
+
+    def _variant(self, obstacle_velocity, goal_xy, via, obs, B):
+        """The variant of a call with these optional inputs: (suffix of the entry point — _rank's choice, the
+        trailing arguments it takes on top of the plain entry point's, the arrays those point into, to be kept
+        alive for the call).  The trailing arguments are the first 0, 1, 2 or 3 of (velocity table shaped like
+        `obs`, goal_xy as B×2, irm_via* with its targets as B×V×D), NULL where that input is not given."""
+        n = _rank(obstacle_velocity is not None, goal_xy is not None, self._has_via(via))
+        vs = tg = None
+        if n == 3:
+            tg = via.padded(B, self.D)
+            vs = _via_struct(via, tg.ctypes.data)
+        vel = None if obstacle_velocity is None else self._velocity(obstacle_velocity, obs)
+        gxy = None if goal_xy is None else self._goal_xy(goal_xy, B)
+        tail = (_ptr(vel), _ptr(gxy), None if vs is None else ctypes.byref(vs))[:n]
+        return _SUFFIX[n], tail, (vel, gxy, vs, tg)
 
     def via_seed(self, start, goal, via, goal_xy=None):
         """α0 ((B×)N×D) through the via-points: the knot configurations start, each via-point in row order and
@@ -453,25 +472,10 @@ class Context:
         s, g = self._sg(start, goal, B)
         obs = _f32(obstacles).reshape(-1, 2)
         out = np.zeros(B, np.float32)
-        vs, vt = self._via(via, B)
-        if vs is not None:
-            vel = None if obstacle_velocity is None else self._velocity(_f32(obstacle_velocity).reshape(-1, 2), obs)
-            gxy = None if goal_xy is None else self._goal_xy(goal_xy, B)
-            check(self.lib.irm_eval_cost_via(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
-                                             float(lsg), float(ljl), float(lmax), _ptr(out), _ptr(vel), _ptr(gxy),
-                                             ctypes.byref(vs)))
-        elif goal_xy is not None:
-            vel = None if obstacle_velocity is None else self._velocity(_f32(obstacle_velocity).reshape(-1, 2), obs)
-            check(self.lib.irm_eval_cost_task(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
-                                              float(lsg), float(ljl), float(lmax), _ptr(out), _ptr(vel),
-                                              _ptr(self._goal_xy(goal_xy, B))))
-        elif obstacle_velocity is None:
-            check(self.lib.irm_eval_cost(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
-                                         float(lsg), float(ljl), float(lmax), _ptr(out)))
-        else:
-            vel = self._velocity(_f32(obstacle_velocity).reshape(-1, 2), obs)
-            check(self.lib.irm_eval_cost_moving(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
-                                                float(lsg), float(ljl), float(lmax), _ptr(out), _ptr(vel)))
+        vel = None if obstacle_velocity is None else _f32(obstacle_velocity).reshape(-1, 2)
+        suffix, tail, _keep = self._variant(vel, goal_xy, via, obs, B)
+        check(getattr(self.lib, "irm_eval_cost" + suffix)(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
+                                                          float(lsg), float(ljl), float(lmax), _ptr(out), *tail))
         return out[0] if single else out
 
     def eval_cost_grad(self, alpha, obstacles, start, goal, lsg, ljl, lmax, with_cost=False, obstacle_velocity=None,
@@ -482,26 +486,11 @@ class Context:
         obs = _f32(obstacles).reshape(-1, 2)
         grad = np.zeros_like(a)
         cost = np.zeros(B, np.float32)
-        vs, vt = self._via(via, B)
-        if vs is not None:
-            vel = None if obstacle_velocity is None else self._velocity(_f32(obstacle_velocity).reshape(-1, 2), obs)
-            gxy = None if goal_xy is None else self._goal_xy(goal_xy, B)
-            check(self.lib.irm_eval_cost_grad_via(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
-                                                  float(lsg), float(ljl), float(lmax), _ptr(grad), _ptr(cost),
-                                                  _ptr(vel), _ptr(gxy), ctypes.byref(vs)))
-        elif goal_xy is not None:
-            vel = None if obstacle_velocity is None else self._velocity(_f32(obstacle_velocity).reshape(-1, 2), obs)
-            check(self.lib.irm_eval_cost_grad_task(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
-                                                   float(lsg), float(ljl), float(lmax), _ptr(grad), _ptr(cost),
-                                                   _ptr(vel), _ptr(self._goal_xy(goal_xy, B))))
-        elif obstacle_velocity is None:
-            check(self.lib.irm_eval_cost_grad(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
-                                              float(lsg), float(ljl), float(lmax), _ptr(grad), _ptr(cost)))
-        else:
-            vel = self._velocity(_f32(obstacle_velocity).reshape(-1, 2), obs)
-            check(self.lib.irm_eval_cost_grad_moving(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs), obs.shape[0], B,
-                                                     float(lsg), float(ljl), float(lmax), _ptr(grad), _ptr(cost),
-                                                     _ptr(vel)))
+        vel = None if obstacle_velocity is None else _f32(obstacle_velocity).reshape(-1, 2)
+        suffix, tail, _keep = self._variant(vel, goal_xy, via, obs, B)
+        check(getattr(self.lib, "irm_eval_cost_grad" + suffix)(self._h, _ptr(a), _ptr(s), _ptr(g), _ptr(obs),
+                                                               obs.shape[0], B, float(lsg), float(ljl), float(lmax),
+                                                               _ptr(grad), _ptr(cost), *tail))
         if single:
             grad, cost = grad[0], cost[0]
         return (grad, cost) if with_cost else grad
@@ -516,28 +505,17 @@ class Context:
         s, g = self._sg(start, goal, B)
         ok = np.zeros(B, np.uint8)
         rep = np.zeros((B, 11), np.float32)
-        vs, vt = self._via(via, B)
-        if vs is not None:
-            dist = np.zeros((B, len(via)), np.float32)
-            gxy = None if goal_xy is None else self._goal_xy(goal_xy, B)
-            check(self.lib.irm_constraints_via(self._h, _ptr(a), _ptr(s), _ptr(g), B, ok.ctypes.data_as(_abi.c_uint8_p),
-                                               _ptr(rep), _ptr(gxy), ctypes.byref(vs), _ptr(dist)))
-            if single:
-                return bool(ok[0]), rep[0], dist[0]
-            return ok.astype(bool), rep, dist
-        if goal_xy is None:
-            check(self.lib.irm_constraints(self._h, _ptr(a), _ptr(s), _ptr(g), B,
-                                           ok.ctypes.data_as(_abi.c_uint8_p), _ptr(rep)))
-        else:
-            check(self.lib.irm_constraints_task(self._h, _ptr(a), _ptr(s), _ptr(g), B,
-                                                ok.ctypes.data_as(_abi.c_uint8_p), _ptr(rep),
-                                                _ptr(self._goal_xy(goal_xy, B))))
-        if via is not None:  # an empty ViaPoints: the existing call, and no distances
-            dist = np.zeros((B, 0), np.float32)
-            return (bool(ok[0]), rep[0], dist[0]) if single else (ok.astype(bool), rep, dist)
+        # no velocity: the twins' trailing arguments start at goal_xy; the _via form adds the distance output
+        suffix, tail, _keep = self._variant(None, goal_xy, via, None, B)
+        dist = None if via is None else np.zeros((B, len(via)), np.float32)  # (an empty ViaPoints: no distances)
+        if suffix == "_via":
+            tail += (_ptr(dist),)
+        check(getattr(self.lib, "irm_constraints" + suffix)(self._h, _ptr(a), _ptr(s), _ptr(g), B,
+                                                            ok.ctypes.data_as(_abi.c_uint8_p), _ptr(rep), *tail[1:]))
+        out = [ok.astype(bool), rep] + ([] if dist is None else [dist])
         if single:
-            return bool(ok[0]), rep[0]
-        return ok.astype(bool), rep
+            out = [bool(ok[0])] + [x[0] for x in out[1:]]
+        return tuple(out)
 
     def fk(self, traj, with_jacobian=False):
         q, single = self._batch(traj, (self.N, self.D))
@@ -583,8 +561,7 @@ class Context:
         the call and its initialisation as they are."""
         s, single = self._batch(start, (self.D,))
         B = s.shape[0]
-        vs, vt = self._via(via, B)
-        if vs is not None:
+        if self._has_via(via):
             via.check_rows(self.N)
             if alpha0 is None:
                 alpha0 = self.via_seed(s, goal, via, goal_xy=goal_xy)
@@ -596,17 +573,10 @@ class Context:
         elif goal is None:
             raise ValueError("optimize() needs a goal configuration or a goal_xy")
         g, _ = self._batch(goal, (self.D,))
-        obs = _f32(obstacles)
-        O = obs.shape[-2] if obs.size else 0
-        if obs.ndim == 3:  # per-problem obstacles B × O × 2: one row of 2·O floats per problem
-            if obs.shape[0] != B or obs.shape[2] != 2:
-                raise ValueError(f"per-problem obstacles must be ({B}, O, 2), got {obs.shape}")
-            if obstacle_stride not in (0, 2 * O):
-                raise ValueError(f"obstacle_stride {obstacle_stride} does not match obstacles {obs.shape}")
-            obstacle_stride = 2 * O
-        elif obs.size and (obs.ndim != 2 or obs.shape[1] != 2):
-            raise ValueError(f"shared obstacles must be (O, 2), got {obs.shape}")
-        elif obstacle_stride:
+        obs, O, stride = self._obstacle_table(obstacles, B)
+        if obs.ndim == 3 and obstacle_stride not in (0, stride):
+            raise ValueError(f"obstacle_stride {obstacle_stride} does not match obstacles {obs.shape}")
+        if obs.ndim != 3 and obstacle_stride:
             raise ValueError("obstacle_stride needs per-problem obstacles of shape (B, O, 2)")
         a0 = None
         if alpha0 is not None:
@@ -616,24 +586,9 @@ class Context:
         stats = (IrmStats * B)()
         cap = self.series_capacity() if series else 0
         ser = np.zeros((B, cap, self.N, self.D), np.float32) if series else None
-        if vs is not None:
-            vel = None if obstacle_velocity is None else self._velocity(obstacle_velocity, obs)
-            check(self.lib.irm_optimize_batch_via(self._h, _ptr(a0), _ptr(s), _ptr(g), _ptr(obs), O,
-                                                  int(obstacle_stride), B, _ptr(alpha), _ptr(traj), stats, _ptr(ser),
-                                                  _ptr(vel), _ptr(gxy), ctypes.byref(vs)))
-        elif gxy is not None:
-            vel = None if obstacle_velocity is None else self._velocity(obstacle_velocity, obs)
-            check(self.lib.irm_optimize_batch_task(self._h, _ptr(a0), _ptr(s), _ptr(g), _ptr(obs), O,
-                                                   int(obstacle_stride), B, _ptr(alpha), _ptr(traj), stats, _ptr(ser),
-                                                   _ptr(vel), _ptr(gxy)))
-        elif obstacle_velocity is None:
-            check(self.lib.irm_optimize_batch(self._h, _ptr(a0), _ptr(s), _ptr(g), _ptr(obs), O, int(obstacle_stride),
-                                              B, _ptr(alpha), _ptr(traj), stats, _ptr(ser)))
-        else:
-            vel = self._velocity(obstacle_velocity, obs)
-            check(self.lib.irm_optimize_batch_moving(self._h, _ptr(a0), _ptr(s), _ptr(g), _ptr(obs), O,
-                                                     int(obstacle_stride), B, _ptr(alpha), _ptr(traj), stats, _ptr(ser),
-                                                     _ptr(vel)))
+        suffix, tail, _keep = self._variant(obstacle_velocity, gxy, via, obs, B)
+        check(getattr(self.lib, "irm_optimize_batch" + suffix)(self._h, _ptr(a0), _ptr(s), _ptr(g), _ptr(obs), O, stride,
+                                                               B, _ptr(alpha), _ptr(traj), stats, _ptr(ser), *tail))
         st = stats_to_dict(stats)
         if single:
             alpha, traj = alpha[0], traj[0]
@@ -667,24 +622,13 @@ class Context:
         its rows and kinds) with via_target_dev, the device address of the targets (batch × V × D fp32):
         irm_optimize_batch_via_dev."""
         vel = obstacle_velocity_dev or getattr(batch_dev, "obstacle_velocity", 0)
-        if via is not None and len(via):
+        n = _rank(vel, goal_xy_dev, via is not None and len(via))
+        # the twins' trailing arguments, then the stream, then the irm_via* (its target a device address)
+        tail = (_dev(vel) if vel else None, _dev(goal_xy_dev) if goal_xy_dev else None)[:n] + (ctypes.c_void_p(stream),)
+        if n == 3:
             via.check_rows(self.N)
-            v = IrmVia()
-            v.n_via = len(via)
-            for i, (r, c) in enumerate(zip(via.rows, via.cartesian)):
-                v.row[i], v.cartesian[i] = r, c
-            v.target = int(via_target_dev) if via_target_dev else None
-            check(self.lib.irm_optimize_batch_via_dev(self._h, ctypes.byref(batch_dev), _dev(vel) if vel else None,
-                                                      _dev(goal_xy_dev) if goal_xy_dev else None,
-                                                      ctypes.c_void_p(stream), ctypes.byref(v)))
-        elif goal_xy_dev:
-            check(self.lib.irm_optimize_batch_task_dev(self._h, ctypes.byref(batch_dev), _dev(vel) if vel else None,
-                                                       _dev(goal_xy_dev), ctypes.c_void_p(stream)))
-        elif not vel:
-            check(self.lib.irm_optimize_batch_dev(self._h, ctypes.byref(batch_dev), ctypes.c_void_p(stream)))
-        else:
-            check(self.lib.irm_optimize_batch_moving_dev(self._h, ctypes.byref(batch_dev), _dev(vel),
-                                                         ctypes.c_void_p(stream)))
+            tail += (ctypes.byref(_via_struct(via, int(via_target_dev) if via_target_dev else None)),)
+        check(getattr(self.lib, "irm_optimize_batch" + _SUFFIX[n] + "_dev")(self._h, ctypes.byref(batch_dev), *tail))
 
 
 def via_path(t, rows, knots):

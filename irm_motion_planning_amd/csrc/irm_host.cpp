@@ -387,12 +387,6 @@ int check_vel(const char* fn, const float* vel, size_t n) {
     return 0;
 }
 
-// a moving launch for which choose_shape found no trajectories-per-workgroup
-int fail_moving_lds(const char* fn, const irm_ctx* c, int O, int stride) {
-    return fail(IRM_EINVAL, "%s: no workgroup shape fits the 160 KiB LDS for N=%d with O=%d %s obstacles and the moving "
-                "table (positions and velocities: twice the obstacle words)", fn, c->N, O, stride ? "per-problem" : "shared");
-}
-
 // a host table of end-effector targets (B×2): every entry finite
 int check_goal_xy(const char* fn, const float* gxy, size_t B) {
     for (size_t i = 0; i < 2 * B; ++i)
@@ -445,27 +439,54 @@ void set_via(KParams& kp, const irm_via* via, int V, const float* target_dev) {
     kp.via_target = target_dev;
 }
 
-// a via launch for which choose_shape found no trajectories-per-workgroup
-int fail_via_lds(const char* fn, const irm_ctx* c) {
-    return fail(IRM_EINVAL, "%s: no workgroup shape fits the 160 KiB LDS for N=%d with the via words", fn, c->N);
+// What a moving, an end-effector-goal and a via call add to the plain one, each nullable: the obstacles'
+// velocities (the obstacle table's shape), the end-effector targets (B×2), the via-points and, of
+// irm_constraints_via, the via distances out (B×V).
+struct Variant {
+    const float* vel = nullptr;
+    const float* gxy = nullptr;
+    const irm_via* via = nullptr;
+    float* vdist = nullptr;
+};
+
+// A variant into a launch's parameters.  dev: the tables on the device (the callers stage host tables
+// themselves), read for a moving / an end-effector-goal launch; its via gives the V rows and kinds, via_target the
+// targets on the device (B×V×D).
+void set_variant(KParams& kp, bool moving, bool task, const Variant& dev, int V, const float* via_target) {
+    if (moving) {
+        kp.moving = 1;
+        kp.obs_vel = dev.vel;
+    }
+    if (task) {
+        kp.task = 1;
+        kp.goal_xy = dev.gxy;
+    }
+    set_via(kp, dev.via, V, via_target);
 }
 
-// Run one forward-family kernel on B host trajectories.  vel (nullable): the obstacles' velocities (O×2);
-// gxy (nullable): the end-effector targets (B×2) of an end-effector-goal call; via (nullable): the via-points,
-// vdist (nullable, mode 3): their distances (B×V).
+// a launch for which choose_shape found no trajectories-per-workgroup; fn_moving, fn_via: the entry point a
+// moving and a via launch are reported under
+int fail_no_shape(const char* fn_moving, const char* fn_via, const irm_ctx* c, const KParams& kp, int O, int stride) {
+    if (kp.moving)
+        return fail(IRM_EINVAL, "%s: no workgroup shape fits the 160 KiB LDS for N=%d with O=%d %s obstacles and the moving "
+                    "table (positions and velocities: twice the obstacle words)", fn_moving, c->N, O, stride ? "per-problem" : "shared");
+    if (kp.via) return fail(IRM_EINVAL, "%s: no workgroup shape fits the 160 KiB LDS for N=%d with the via words", fn_via, c->N);
+    return fail(IRM_EINVAL, "no workgroup shape fits LDS");
+}
+
+// Run one forward-family kernel on B host trajectories (v: host tables; v.vdist with mode 3).
 int run_forward(irm_ctx* c, int mode, const float* alpha, const float* start, const float* goal, const float* obs,
                 int O, int B, float lsg, float ljl, float lmax, int which, float* out0, float* out1, uint8_t* ok,
-                const float* vel = nullptr, const float* gxy = nullptr, const irm_via* via = nullptr,
-                float* vdist = nullptr) {
+                Variant v) {
     if (set_device(c)) return IRM_EDEVICE;
     if (B < 0 || !alpha) return fail(IRM_EINVAL, "bad batch arguments");
     int V = 0;
-    if (check_via("irm_eval_cost(_grad)_via / irm_constraints_via", c, via, (size_t)std::max(B, 0), true, B > 0, &V))
+    if (check_via("irm_eval_cost(_grad)_via / irm_constraints_via", c, v.via, (size_t)std::max(B, 0), true, B > 0, &V))
         return IRM_EINVAL;
     if (check_obs(O)) return IRM_EINVAL;
-    if (!obs || O == 0) vel = nullptr;  // no obstacle, nothing moves
-    if (vel && check_vel("irm_eval_cost(_grad)_moving", vel, (size_t)O * 2)) return IRM_EINVAL;
-    if (gxy && check_goal_xy("irm_eval_cost(_grad)_task / irm_constraints_task", gxy, (size_t)B)) return IRM_EINVAL;
+    if (!obs || O == 0) v.vel = nullptr;  // no obstacle, nothing moves
+    if (v.vel && check_vel("irm_eval_cost(_grad)_moving", v.vel, (size_t)O * 2)) return IRM_EINVAL;
+    if (v.gxy && check_goal_xy("irm_eval_cost(_grad)_task / irm_constraints_task", v.gxy, (size_t)B)) return IRM_EINVAL;
     if (B == 0) return IRM_OK;
     const int N = c->N, D = c->D;
     const size_t nd = (size_t)B * N * D;
@@ -483,24 +504,15 @@ int run_forward(irm_ctx* c, int mode, const float* alpha, const float* start, co
     HIP_TRY(hipMemcpyAsync(d + o_s, start ? start : zeros.data(), (size_t)B * D * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_g, goal ? goal : zeros.data(), (size_t)B * D * 4, hipMemcpyHostToDevice, s));
     if (O > 0 && obs) HIP_TRY(hipMemcpyAsync(d + o_obs, obs, (size_t)O * 8, hipMemcpyHostToDevice, s));
-    if (vel) HIP_TRY(hipMemcpyAsync(d + o_vel, vel, (size_t)O * 8, hipMemcpyHostToDevice, s));
+    if (v.vel) HIP_TRY(hipMemcpyAsync(d + o_vel, v.vel, (size_t)O * 8, hipMemcpyHostToDevice, s));
     KParams kp = c->kp;
     kp.B = B;
     kp.O = (obs ? O : 0);
     kp.obs_stride = 0;
-    if (vel) {
-        kp.moving = 1;
-        kp.obs_vel = (const float*)(d + o_vel);
-    }
-    if (gxy) {
-        HIP_TRY(hipMemcpyAsync(d + o_gxy, gxy, (size_t)B * 8, hipMemcpyHostToDevice, s));
-        kp.task = 1;
-        kp.goal_xy = (const float*)(d + o_gxy);
-    }
-    if (V > 0) {
-        HIP_TRY(hipMemcpyAsync(d + o_via, via->target, (size_t)B * V * D * 4, hipMemcpyHostToDevice, s));
-        set_via(kp, via, V, (const float*)(d + o_via));
-    }
+    if (v.gxy) HIP_TRY(hipMemcpyAsync(d + o_gxy, v.gxy, (size_t)B * 8, hipMemcpyHostToDevice, s));
+    if (V > 0) HIP_TRY(hipMemcpyAsync(d + o_via, v.via->target, (size_t)B * V * D * 4, hipMemcpyHostToDevice, s));
+    set_variant(kp, v.vel != nullptr, v.gxy != nullptr, {(const float*)(d + o_vel), (const float*)(d + o_gxy), v.via}, V,
+                (const float*)(d + o_via));
     kp.alpha0 = (const float*)(d + o_alpha);
     kp.start = (const float*)(d + o_s);
     kp.goal = (const float*)(d + o_g);
@@ -514,8 +526,7 @@ int run_forward(irm_ctx* c, int mode, const float* alpha, const float* start, co
     kp.out1 = (float*)(d + o_out1);
     kp.out_ok = (uint8_t*)(d + o_ok);
     if (choose_shape(c, B, false, kp, nullptr) <= 0)
-        return vel ? fail_moving_lds("irm_eval_cost(_grad)_moving", c, O, 0)
-                   : V > 0 ? fail_via_lds("irm_eval_cost(_grad)_via", c) : fail(IRM_EINVAL, "no workgroup shape fits LDS");
+        return fail_no_shape("irm_eval_cost(_grad)_moving", "irm_eval_cost(_grad)_via", c, kp, O, 0);
     HIP_TRY(irm::launch_forward(kp, mode, s));
     if (out0) {
         size_t bytes = (mode == 0) ? nd * 4 : (mode == 3 ? (size_t)B * 11 * 4 : (size_t)B * 4);
@@ -523,7 +534,7 @@ int run_forward(irm_ctx* c, int mode, const float* alpha, const float* start, co
     }
     if (out1) HIP_TRY(hipMemcpyAsync(out1, d + o_out1, nd * 4, hipMemcpyDeviceToHost, s));
     // (mode 3 of a via call: the kernel wrote the via distances through out1, B×V ≤ B×N×D words)
-    if (vdist && V > 0) HIP_TRY(hipMemcpyAsync(vdist, d + o_out1, (size_t)B * V * 4, hipMemcpyDeviceToHost, s));
+    if (v.vdist && V > 0) HIP_TRY(hipMemcpyAsync(v.vdist, d + o_out1, (size_t)B * V * 4, hipMemcpyDeviceToHost, s));
     if (ok) HIP_TRY(hipMemcpyAsync(ok, d + o_ok, (size_t)B, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return IRM_OK;
@@ -534,19 +545,19 @@ int run_forward(irm_ctx* c, int mode, const float* alpha, const float* start, co
 int irm_evaluate(irm_ctx* c, const float* alpha, int32_t B, int32_t which, float* out) {
     if (!c || !out) return fail(IRM_EINVAL, "irm_evaluate: null argument");
     return run_forward(c, 0, alpha, nullptr, nullptr, nullptr, 0, B, 0.f, 0.f, 0.f, which ? 1 : 0, out, nullptr,
-                       nullptr);
+                       nullptr, {});
 }
 
 int irm_eval_cost(irm_ctx* c, const float* alpha, const float* start, const float* goal, const float* obstacles,
                   int32_t O, int32_t B, float lsg, float ljl, float lmax, float* cost_out) {
     if (!c || !cost_out || !start || !goal) return fail(IRM_EINVAL, "irm_eval_cost: null argument");
-    return run_forward(c, 1, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, nullptr, nullptr);
+    return run_forward(c, 1, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, nullptr, nullptr, {});
 }
 
 int irm_eval_cost_grad(irm_ctx* c, const float* alpha, const float* start, const float* goal, const float* obstacles,
                        int32_t O, int32_t B, float lsg, float ljl, float lmax, float* grad_out, float* cost_out) {
     if (!c || !grad_out || !start || !goal) return fail(IRM_EINVAL, "irm_eval_cost_grad: null argument");
-    return run_forward(c, 2, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, grad_out, nullptr);
+    return run_forward(c, 2, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, grad_out, nullptr, {});
 }
 
 int irm_eval_cost_moving(irm_ctx* c, const float* alpha, const float* start, const float* goal, const float* obstacles,
@@ -554,7 +565,7 @@ int irm_eval_cost_moving(irm_ctx* c, const float* alpha, const float* start, con
                          const float* obstacle_velocity) {
     if (!c || !cost_out || !start || !goal) return fail(IRM_EINVAL, "irm_eval_cost_moving: null argument");
     return run_forward(c, 1, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, nullptr, nullptr,
-                       obstacle_velocity);
+                       {obstacle_velocity});
 }
 
 int irm_eval_cost_grad_moving(irm_ctx* c, const float* alpha, const float* start, const float* goal,
@@ -562,13 +573,13 @@ int irm_eval_cost_grad_moving(irm_ctx* c, const float* alpha, const float* start
                               float* grad_out, float* cost_out, const float* obstacle_velocity) {
     if (!c || !grad_out || !start || !goal) return fail(IRM_EINVAL, "irm_eval_cost_grad_moving: null argument");
     return run_forward(c, 2, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, grad_out, nullptr,
-                       obstacle_velocity);
+                       {obstacle_velocity});
 }
 
 int irm_constraints(irm_ctx* c, const float* alpha, const float* start, const float* goal, int32_t B, uint8_t* ok_out,
                     float* report_out) {
     if (!c || !ok_out || !start || !goal) return fail(IRM_EINVAL, "irm_constraints: null argument");
-    return run_forward(c, 3, alpha, start, goal, nullptr, 0, B, 0.f, 0.f, 0.f, 0, report_out, nullptr, ok_out);
+    return run_forward(c, 3, alpha, start, goal, nullptr, 0, B, 0.f, 0.f, 0.f, 0, report_out, nullptr, ok_out, {});
 }
 
 int irm_eval_cost_task(irm_ctx* c, const float* alpha, const float* start, const float* goal, const float* obstacles,
@@ -576,7 +587,7 @@ int irm_eval_cost_task(irm_ctx* c, const float* alpha, const float* start, const
                        const float* obstacle_velocity, const float* goal_xy) {
     if (!c || !cost_out || !start || !goal) return fail(IRM_EINVAL, "irm_eval_cost_task: null argument");
     return run_forward(c, 1, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, nullptr, nullptr,
-                       obstacle_velocity, goal_xy);
+                       {obstacle_velocity, goal_xy});
 }
 
 int irm_eval_cost_grad_task(irm_ctx* c, const float* alpha, const float* start, const float* goal,
@@ -584,14 +595,14 @@ int irm_eval_cost_grad_task(irm_ctx* c, const float* alpha, const float* start, 
                             float* grad_out, float* cost_out, const float* obstacle_velocity, const float* goal_xy) {
     if (!c || !grad_out || !start || !goal) return fail(IRM_EINVAL, "irm_eval_cost_grad_task: null argument");
     return run_forward(c, 2, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, grad_out, nullptr,
-                       obstacle_velocity, goal_xy);
+                       {obstacle_velocity, goal_xy});
 }
 
 int irm_constraints_task(irm_ctx* c, const float* alpha, const float* start, const float* goal, int32_t B,
                          uint8_t* ok_out, float* report_out, const float* goal_xy) {
     if (!c || !ok_out || !start || !goal) return fail(IRM_EINVAL, "irm_constraints_task: null argument");
-    return run_forward(c, 3, alpha, start, goal, nullptr, 0, B, 0.f, 0.f, 0.f, 0, report_out, nullptr, ok_out, nullptr,
-                       goal_xy);
+    return run_forward(c, 3, alpha, start, goal, nullptr, 0, B, 0.f, 0.f, 0.f, 0, report_out, nullptr, ok_out,
+                       {nullptr, goal_xy});
 }
 
 int irm_eval_cost_via(irm_ctx* c, const float* alpha, const float* start, const float* goal, const float* obstacles,
@@ -599,7 +610,7 @@ int irm_eval_cost_via(irm_ctx* c, const float* alpha, const float* start, const 
                       const float* obstacle_velocity, const float* goal_xy, const irm_via* via) {
     if (!c || !cost_out || !start || !goal) return fail(IRM_EINVAL, "irm_eval_cost_via: null argument");
     return run_forward(c, 1, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, nullptr, nullptr,
-                       obstacle_velocity, goal_xy, via);
+                       {obstacle_velocity, goal_xy, via});
 }
 
 int irm_eval_cost_grad_via(irm_ctx* c, const float* alpha, const float* start, const float* goal,
@@ -608,15 +619,15 @@ int irm_eval_cost_grad_via(irm_ctx* c, const float* alpha, const float* start, c
                            const irm_via* via) {
     if (!c || !grad_out || !start || !goal) return fail(IRM_EINVAL, "irm_eval_cost_grad_via: null argument");
     return run_forward(c, 2, alpha, start, goal, obstacles, O, B, lsg, ljl, lmax, 0, cost_out, grad_out, nullptr,
-                       obstacle_velocity, goal_xy, via);
+                       {obstacle_velocity, goal_xy, via});
 }
 
 int irm_constraints_via(irm_ctx* c, const float* alpha, const float* start, const float* goal, int32_t B,
                         uint8_t* ok_out, float* report_out, const float* goal_xy, const irm_via* via,
                         float* via_dist_out) {
     if (!c || !ok_out || !start || !goal) return fail(IRM_EINVAL, "irm_constraints_via: null argument");
-    return run_forward(c, 3, alpha, start, goal, nullptr, 0, B, 0.f, 0.f, 0.f, 0, report_out, nullptr, ok_out, nullptr,
-                       goal_xy, via, via_dist_out);
+    return run_forward(c, 3, alpha, start, goal, nullptr, 0, B, 0.f, 0.f, 0.f, 0, report_out, nullptr, ok_out,
+                       {nullptr, goal_xy, via, via_dist_out});
 }
 
 int irm_ik_seed_dev(irm_ctx* c, const float* start_dev, const float* goal_xy_dev, int32_t B, float* q_dev,
@@ -750,15 +761,12 @@ int irm_init_alpha(irm_ctx* c, const float* start, const float* goal, int32_t B,
 
 namespace {
 
-// irm_optimize_batch_dev / irm_optimize_batch_moving_dev / irm_optimize_batch_task_dev (vel, gxy: device
-// pointers, NULL for static obstacles / the joint goal)
-// via (nullable): the via-points, its target a device pointer
-int optimize_dev(irm_ctx* c, const irm_batch_dev* a, const float* vel, void* stream, const float* gxy = nullptr,
-                 const irm_via* via = nullptr) {
+// irm_optimize_batch_dev and its _moving, _task and _via twins (v: device pointers, the via target too)
+int optimize_dev(irm_ctx* c, const irm_batch_dev* a, const Variant& v, void* stream) {
     if (!c || !a) return fail(IRM_EINVAL, "irm_optimize_batch_dev: null argument");
     if (a->batch < 0 || !a->start || !a->goal) return fail(IRM_EINVAL, "bad batch arguments");
     int V = 0;
-    if (check_via("irm_optimize_batch_via", c, via, (size_t)a->batch, false, a->batch > 0, &V)) return IRM_EINVAL;
+    if (check_via("irm_optimize_batch_via", c, v.via, (size_t)a->batch, false, a->batch > 0, &V)) return IRM_EINVAL;
     if (check_obs(a->n_obstacles) || check_stride(a->n_obstacles, a->obstacle_stride)) return IRM_EINVAL;
     if (a->n_obstacles > 0 && !a->obstacles) return fail(IRM_EINVAL, "obstacles pointer missing");
     if (set_device(c)) return IRM_EDEVICE;
@@ -777,19 +785,9 @@ int optimize_dev(irm_ctx* c, const irm_batch_dev* a, const float* vel, void* str
     kp.series = a->series_out;
     kp.trace = c->d_trace;
     kp.trace_cap = c->trace_cap;
-    if (vel && a->n_obstacles > 0) {
-        kp.moving = 1;
-        kp.obs_vel = vel;
-    }
-    if (gxy) {
-        kp.task = 1;
-        kp.goal_xy = gxy;
-    }
-    if (V > 0) set_via(kp, via, V, via->target);
+    set_variant(kp, v.vel && a->n_obstacles > 0, v.gxy != nullptr, v, V, V > 0 ? v.via->target : nullptr);
     if (choose_shape(c, a->batch, true, kp, nullptr) <= 0)
-        return kp.moving ? fail_moving_lds("irm_optimize_batch_moving", c, a->n_obstacles, a->obstacle_stride)
-               : V > 0   ? fail_via_lds("irm_optimize_batch_via", c)
-                         : fail(IRM_EINVAL, "no workgroup shape fits LDS");
+        return fail_no_shape("irm_optimize_batch_moving", "irm_optimize_batch_via", c, kp, a->n_obstacles, a->obstacle_stride);
 #if defined(IRM_PHASE_PROFILE) || defined(IRM_DIV_CHECK)
     {  // (IRM_DIV_CHECK: per-block counters of the BLS division check, zeroed per launch)
         const int grid = (a->batch + kp.TB - 1) / kp.TB;
@@ -810,8 +808,9 @@ int optimize_dev(irm_ctx* c, const irm_batch_dev* a, const float* vel, void* str
     return IRM_OK;
 }
 
-int optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series, bool moving,
-                  irm_launch_plan* out, bool task = false, const irm_via* via = nullptr) {
+// irm_optimize_plan and its twins: a moving / an end-effector-goal launch is named without its tables
+int optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series, bool moving, bool task,
+                  const irm_via* via, irm_launch_plan* out) {
     if (!c || !out || batch <= 0) return fail(IRM_EINVAL, "irm_optimize_plan: bad argument");
     if (check_obs(n_obstacles)) return IRM_EINVAL;
     int V = 0;
@@ -823,13 +822,9 @@ int optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t 
     // the series flow runs when the context records it (irm_params.record_series) or the call asks
     // for the series (irm_optimize_batch with series_out) — as in irm_optimize_batch(_dev)
     kp.record_series = (c->kp.record_series || record_series) ? 1 : 0;
-    kp.moving = (moving && n_obstacles > 0) ? 1 : 0;
-    kp.task = task ? 1 : 0;
-    if (V > 0) set_via(kp, via, V, nullptr);
+    set_variant(kp, moving && n_obstacles > 0, task, {nullptr, nullptr, via}, V, nullptr);
     if (choose_shape(c, batch, true, kp, nullptr) <= 0)
-        return kp.moving ? fail_moving_lds("irm_optimize_plan_moving", c, n_obstacles, 0)
-               : V > 0   ? fail_via_lds("irm_optimize_plan_via", c)
-                         : fail(IRM_EINVAL, "no workgroup shape fits LDS");
+        return fail_no_shape("irm_optimize_plan_moving", "irm_optimize_plan_via", c, kp, n_obstacles, 0);
     irm::LaunchDesc d{};
     d.describe_only = true;
     HIP_TRY(irm::launch_optimize(kp, nullptr, &d));  // the dispatch fills d and launches nothing
@@ -853,40 +848,40 @@ int optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t 
 
 extern "C" {
 
-int irm_optimize_batch_dev(irm_ctx* c, const irm_batch_dev* a, void* stream) { return optimize_dev(c, a, nullptr, stream); }
+int irm_optimize_batch_dev(irm_ctx* c, const irm_batch_dev* a, void* stream) { return optimize_dev(c, a, {}, stream); }
 
 int irm_optimize_batch_moving_dev(irm_ctx* c, const irm_batch_dev* a, const float* obstacle_velocity_dev, void* stream) {
-    return optimize_dev(c, a, obstacle_velocity_dev, stream);
+    return optimize_dev(c, a, {obstacle_velocity_dev}, stream);
 }
 
 int irm_optimize_plan(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series,
                       irm_launch_plan* out) {
-    return optimize_plan(c, batch, n_obstacles, record_series, false, out);
+    return optimize_plan(c, batch, n_obstacles, record_series, false, false, nullptr, out);
 }
 
 int irm_optimize_plan_moving(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series,
                              irm_launch_plan* out) {
-    return optimize_plan(c, batch, n_obstacles, record_series, true, out);
+    return optimize_plan(c, batch, n_obstacles, record_series, true, false, nullptr, out);
 }
 
 int irm_optimize_batch_task_dev(irm_ctx* c, const irm_batch_dev* a, const float* obstacle_velocity_dev,
                                 const float* goal_xy_dev, void* stream) {
-    return optimize_dev(c, a, obstacle_velocity_dev, stream, goal_xy_dev);
+    return optimize_dev(c, a, {obstacle_velocity_dev, goal_xy_dev}, stream);
 }
 
 int irm_optimize_plan_task(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series,
                            irm_launch_plan* out) {
-    return optimize_plan(c, batch, n_obstacles, record_series, false, out, true);
+    return optimize_plan(c, batch, n_obstacles, record_series, false, true, nullptr, out);
 }
 
 int irm_optimize_batch_via_dev(irm_ctx* c, const irm_batch_dev* a, const float* obstacle_velocity_dev,
                                const float* goal_xy_dev, void* stream, const irm_via* via) {
-    return optimize_dev(c, a, obstacle_velocity_dev, stream, goal_xy_dev, via);
+    return optimize_dev(c, a, {obstacle_velocity_dev, goal_xy_dev, via}, stream);
 }
 
 int irm_optimize_plan_via(const irm_ctx* c, int32_t batch, int32_t n_obstacles, int32_t record_series,
                           irm_launch_plan* out, const irm_via* via) {
-    return optimize_plan(c, batch, n_obstacles, record_series, false, out, true, via);
+    return optimize_plan(c, batch, n_obstacles, record_series, false, true, via, out);
 }
 
 int irm_set_work_queue(irm_ctx* c, int32_t groups) {
@@ -1000,6 +995,14 @@ int irm_eval_any(irm_ctx* c, const float* alpha, int32_t B, int32_t which, float
 
 namespace {
 
+// the velocity table (a device pointer, nullable) of a launch on the evaluation times, after kp.O is set
+void set_moving_eval(KParams& kp, const irm_ctx* c, const float* vel) {
+    if (!vel || kp.O <= 0) return;
+    kp.moving = 1;  // sample i sees the table at t_eval[i]
+    kp.obs_vel = vel;
+    kp.tsup = c->d_teval;
+}
+
 // irm_dense_check(_moving)_dev: vel a device pointer, NULL for the static check
 int dense_check_dev(irm_ctx* c, const float* alpha, const float* obstacles, int32_t O, int32_t obstacle_stride,
                     int32_t B, irm_dense_report* report, float* cost, const float* vel, void* stream) {
@@ -1016,11 +1019,7 @@ int dense_check_dev(irm_ctx* c, const float* alpha, const float* obstacles, int3
     kp.obs_stride = obstacle_stride;
     kp.alpha0 = alpha;
     kp.obstacles = obstacles;
-    if (vel && O > 0) {  // sample i sees the table at t_eval[i]
-        kp.moving = 1;
-        kp.obs_vel = vel;
-        kp.tsup = c->d_teval;
-    }
+    set_moving_eval(kp, c, vel);
     HIP_TRY(irm::launch_dense_check(kp, c->d_KqT, c->d_dKqT, (int)c->t_eval.size(), report, cost, (hipStream_t)stream));
     return IRM_OK;
 }
@@ -1126,11 +1125,7 @@ int irm_clearance_dev(irm_ctx* c, const float* alpha, const float* obstacles, in
     kp.obs_stride = obstacle_stride;
     kp.alpha0 = alpha;
     kp.obstacles = obstacles;
-    if (vel && O > 0) {  // sample i sees the table at t_eval[i]
-        kp.moving = 1;
-        kp.obs_vel = vel;
-        kp.tsup = c->d_teval;
-    }
+    set_moving_eval(kp, c, vel);
     HIP_TRY(irm::launch_clearance(kp, c->d_KqT, (int)c->t_eval.size(), O > 0 ? radius : nullptr, obstacle_stride / 2,
                                   link_radius, report, clear, link, joints, (hipStream_t)stream));
     return IRM_OK;
@@ -1490,21 +1485,20 @@ namespace {
 
 int optimize_host(irm_ctx* c, const float* alpha0, const float* start, const float* goal, const float* obstacles,
                   int32_t O, int32_t obstacle_stride, int32_t B, float* alpha_out, float* traj_out,
-                  irm_stats* stats_out, float* series_out, const float* vel, const float* gxy = nullptr,
-                  const irm_via* via = nullptr) {
+                  irm_stats* stats_out, float* series_out, Variant v) {
     if (!c || !start || !goal) return fail(IRM_EINVAL, "irm_optimize_batch: null argument");
     if (check_obs(O) || check_stride(O, obstacle_stride)) return IRM_EINVAL;
     if (set_device(c)) return IRM_EDEVICE;
     int V = 0;
-    if (check_via("irm_optimize_batch_via", c, via, (size_t)std::max(B, 0), true, B > 0, &V)) return IRM_EINVAL;
+    if (check_via("irm_optimize_batch_via", c, v.via, (size_t)std::max(B, 0), true, B > 0, &V)) return IRM_EINVAL;
     if (B <= 0) return B == 0 ? IRM_OK : fail(IRM_EINVAL, "negative batch");
     const int N = c->N, D = c->D;
     const size_t nd = (size_t)B * N * D;
     const size_t nobs = obstacle_stride ? (size_t)B * obstacle_stride : (size_t)O * 2;
     const size_t nser = series_out ? (size_t)B * c->max_series * N * D : 0;
-    if (!obstacles || O == 0) vel = nullptr;
-    if (vel && check_vel("irm_optimize_batch_moving", vel, nobs)) return IRM_EINVAL;
-    if (gxy && check_goal_xy("irm_optimize_batch_task", gxy, (size_t)B)) return IRM_EINVAL;
+    if (!obstacles || O == 0) v.vel = nullptr;
+    if (v.vel && check_vel("irm_optimize_batch_moving", v.vel, nobs)) return IRM_EINVAL;
+    if (v.gxy && check_goal_xy("irm_optimize_batch_task", v.gxy, (size_t)B)) return IRM_EINVAL;
     Stage st{c};
     const size_t o_a0 = st.take(nd * 4), o_s = st.take((size_t)B * D * 4), o_g = st.take((size_t)B * D * 4),
                  o_o = st.take(std::max<size_t>(nobs, 1) * 4), o_ao = st.take(nd * 4), o_to = st.take(nd * 4),
@@ -1514,18 +1508,18 @@ int optimize_host(irm_ctx* c, const float* alpha0, const float* start, const flo
     if (ensure_io(c, st.off)) return IRM_ENOMEM;
     char* d = st.base();
     hipStream_t s = c->stream;
-    if (gxy) HIP_TRY(hipMemcpyAsync(d + o_p, gxy, (size_t)B * 8, hipMemcpyHostToDevice, s));
+    if (v.gxy) HIP_TRY(hipMemcpyAsync(d + o_p, v.gxy, (size_t)B * 8, hipMemcpyHostToDevice, s));
     irm_via vdev{};
     if (V > 0) {
-        HIP_TRY(hipMemcpyAsync(d + o_via, via->target, (size_t)B * V * D * 4, hipMemcpyHostToDevice, s));
-        vdev = *via;
+        HIP_TRY(hipMemcpyAsync(d + o_via, v.via->target, (size_t)B * V * D * 4, hipMemcpyHostToDevice, s));
+        vdev = *v.via;
         vdev.target = (const float*)(d + o_via);
     }
     if (alpha0) HIP_TRY(hipMemcpyAsync(d + o_a0, alpha0, nd * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_s, start, (size_t)B * D * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d + o_g, goal, (size_t)B * D * 4, hipMemcpyHostToDevice, s));
     if (nobs && obstacles) HIP_TRY(hipMemcpyAsync(d + o_o, obstacles, nobs * 4, hipMemcpyHostToDevice, s));
-    if (vel) HIP_TRY(hipMemcpyAsync(d + o_w, vel, nobs * 4, hipMemcpyHostToDevice, s));
+    if (v.vel) HIP_TRY(hipMemcpyAsync(d + o_w, v.vel, nobs * 4, hipMemcpyHostToDevice, s));
     irm_batch_dev a{};
     a.alpha0 = alpha0 ? (const float*)(d + o_a0) : nullptr;
     a.start = (const float*)(d + o_s);
@@ -1540,8 +1534,8 @@ int optimize_host(irm_ctx* c, const float* alpha0, const float* start, const flo
     a.series_out = series_out ? (float*)(d + o_se) : nullptr;
     KParams save = c->kp;
     if (series_out) c->kp.record_series = 1;
-    int rc = optimize_dev(c, &a, vel ? (const float*)(d + o_w) : nullptr, s, gxy ? (const float*)(d + o_p) : nullptr,
-                          V > 0 ? &vdev : nullptr);
+    int rc = optimize_dev(c, &a, {v.vel ? (const float*)(d + o_w) : nullptr, v.gxy ? (const float*)(d + o_p) : nullptr,
+                                  V > 0 ? &vdev : nullptr}, s);
     c->kp = save;
     if (rc) return rc;
     if (alpha_out) HIP_TRY(hipMemcpyAsync(alpha_out, d + o_ao, nd * 4, hipMemcpyDeviceToHost, s));
@@ -1560,7 +1554,7 @@ int irm_optimize_batch(irm_ctx* c, const float* alpha0, const float* start, cons
                        int32_t O, int32_t obstacle_stride, int32_t B, float* alpha_out, float* traj_out,
                        irm_stats* stats_out, float* series_out) {
     return optimize_host(c, alpha0, start, goal, obstacles, O, obstacle_stride, B, alpha_out, traj_out, stats_out,
-                         series_out, nullptr);
+                         series_out, {});
 }
 
 int irm_optimize_batch_moving(irm_ctx* c, const float* alpha0, const float* start, const float* goal,
@@ -1568,7 +1562,7 @@ int irm_optimize_batch_moving(irm_ctx* c, const float* alpha0, const float* star
                               float* traj_out, irm_stats* stats_out, float* series_out,
                               const float* obstacle_velocity) {
     return optimize_host(c, alpha0, start, goal, obstacles, O, obstacle_stride, B, alpha_out, traj_out, stats_out,
-                         series_out, obstacle_velocity);
+                         series_out, {obstacle_velocity});
 }
 
 int irm_optimize_batch_task(irm_ctx* c, const float* alpha0, const float* start, const float* goal,
@@ -1576,7 +1570,7 @@ int irm_optimize_batch_task(irm_ctx* c, const float* alpha0, const float* start,
                             float* traj_out, irm_stats* stats_out, float* series_out, const float* obstacle_velocity,
                             const float* goal_xy) {
     return optimize_host(c, alpha0, start, goal, obstacles, O, obstacle_stride, B, alpha_out, traj_out, stats_out,
-                         series_out, obstacle_velocity, goal_xy);
+                         series_out, {obstacle_velocity, goal_xy});
 }
 
 int irm_optimize_batch_via(irm_ctx* c, const float* alpha0, const float* start, const float* goal,
@@ -1584,7 +1578,7 @@ int irm_optimize_batch_via(irm_ctx* c, const float* alpha0, const float* start, 
                            float* traj_out, irm_stats* stats_out, float* series_out, const float* obstacle_velocity,
                            const float* goal_xy, const irm_via* via) {
     return optimize_host(c, alpha0, start, goal, obstacles, O, obstacle_stride, B, alpha_out, traj_out, stats_out,
-                         series_out, obstacle_velocity, goal_xy, via);
+                         series_out, {obstacle_velocity, goal_xy, via});
 }
 
 }  // extern "C"
