@@ -2,9 +2,10 @@
 
     python -m irm_motion_planning_amd.build [--force] [--prof] [-j N]
 
-The optimiser templates (csrc/irm_kernels_impl.hpp and the part headers it
-includes: irm_wave / irm_prof / irm_physics / irm_opt_common /
-irm_dispatch / irm_launch_decl .hpp) are
+The optimiser templates (csrc/irm_kernels_impl.hpp: k_optimize and k_lean, and the headers it
+includes: irm_lean_plan.hpp, k_lean's schedule, irm_alpha_exact.hpp, irm_k_forward.hpp,
+irm_launch.hpp, the launchers, and the part headers irm_wave / irm_prof / irm_physics /
+irm_opt_common / irm_dispatch / irm_launch_decl .hpp) are
 instantiated in one object per problem shape (csrc/irm_opt_inst.hip compiled
 with IRM_INST_*), so the objects build in parallel; the host-API kernels and dispatch
 (irm_kernels.hip), the kernels of their own units (irm_dense.hip, irm_clearance.hip, irm_fit.hip; irm_dense_sample.hpp is
@@ -42,9 +43,9 @@ CFLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wall", "-Wno
           "-ffp-contract=off", "-fno-slp-vectorize",
           "-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]
 FIX_SHAPES = [(3, 50), (3, 64), (3, 128), (3, 256), (7, 128), (7, 256)]  # IRM_FIX_SHAPES in irm_launch_decl.hpp
-DENSE_SHAPES = [(7, 256)]  # the dense operator's k_lean (irm_kernels.hip launch_optimize)
-QUEUE_SHAPES = [(3, 50), (3, 64), (3, 128), (7, 128)]  # the work queue's k_lean (IRM_QUEUE_SHAPES in irm_kernels_impl.hpp)
-MAX_D = 8
+DENSE_SHAPES = [(7, 256)]  # the dense operator's k_lean (IRM_DENSE_SHAPES in irm_launch_decl.hpp)
+QUEUE_SHAPES = [(3, 50), (3, 64), (3, 128), (7, 128)]  # the work queue's k_lean (IRM_QUEUE_SHAPES in irm_launch_decl.hpp)
+MAX_D = 8  # the DynShape units' D = 1 … MAX_D (IRM_DYN_DIMS in irm_launch_decl.hpp)
 
 VARIANTS = {
     "": ("libirm_hip.so", []),

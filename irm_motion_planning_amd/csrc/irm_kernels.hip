@@ -10,9 +10,8 @@
 namespace irm {
 
 IRM_FIX_SHAPES(IRM_EXTERN_FIX)
-IRM_EXTERN_DENSE(7, 256)
-IRM_EXTERN_DYN(1) IRM_EXTERN_DYN(2) IRM_EXTERN_DYN(3) IRM_EXTERN_DYN(4)
-IRM_EXTERN_DYN(5) IRM_EXTERN_DYN(6) IRM_EXTERN_DYN(7) IRM_EXTERN_DYN(8)
+IRM_DENSE_SHAPES(IRM_EXTERN_DENSE)
+IRM_DYN_DIMS(IRM_EXTERN_DYN)
 
 // ------------------------------------------- per-waypoint utility kernels
 // robot.py:29-36 + 75-87 for B×N waypoints.
@@ -203,11 +202,15 @@ hipError_t launch_optimize(const KParams& p, hipStream_t s, LaunchDesc* desc) {
     // (a moving launch runs k_optimize<DynShape<D>>, as a whole-robot launch does: the shape-specialised
     // kernels have no moving variant, and k_optimize has no work queue; an end-effector-goal launch, p.task,
     // and a via launch, p.via, likewise)
-    if (p.v_ident && p.D == 7 && p.N == 256 && p.RP == p.NK && !p.whole_robot && !p.moving && !p.task && !p.via &&
-        p.lean_ok) {
-        bool served = false;
-        const hipError_t e = launch_dense_shape<DenseShape<7, 256>>(p, s, desc, &served);
-        if (served) return e;
+    if (p.v_ident && p.RP == p.NK && !p.whole_robot && !p.moving && !p.task && !p.via && p.lean_ok) {
+#define IRM_TRY_DENSE(D_, N_)                                                                         \
+        if (p.D == D_ && p.N == N_) {                                                                 \
+            bool served = false;                                                                      \
+            const hipError_t e = launch_dense_shape<DenseShape<D_, N_>>(p, s, desc, &served); \
+            if (served) return e;                                                                     \
+        }
+        IRM_DENSE_SHAPES(IRM_TRY_DENSE)
+#undef IRM_TRY_DENSE
     }
     // shape-specialised kernels for the common configurations (auto rank R = 32)
     if (p.RP == 32 && p.nsplit == stage1_splits(p.NK) && !p.whole_robot && !p.moving && !p.task && !p.via) {

@@ -1,8 +1,8 @@
 // irm_kernels_impl.hpp — gfx950 (CDNA4) kernel templates of the RKHS trajectory optimiser.
-// The optimiser kernels, k_forward and their launchers; included by the instantiation units
-// irm_opt_inst.hip (one k_optimize shape / k_forward D per object, compiled in parallel).
-// The helpers lie in part headers (below): irm_kernels.hip, irm_dense.hip and irm_fit.hip
-// include the parts they use and not this file.
+// The optimiser kernels k_optimize and k_lean, then (last lines) the headers of k_forward and the launchers;
+// included by the instantiation units irm_opt_inst.hip (one k_optimize shape / k_forward D per object,
+// compiled in parallel).  The helpers lie in part headers (below): irm_kernels.hip, irm_dense.hip and
+// irm_fit.hip include the parts they use and not this file.
 //
 // Hot path of simongroeger/irm_motion_planning: optimizer_GD.py:173-232 and
 // optimizer_BLS.py:126-213 over trajectory.py:271-297 / robot.py:29-87 /
@@ -33,209 +33,16 @@
 
 #include "irm_kernels.hpp"
 // the parts cut out so far (each includes what it needs)
+#include "irm_alpha_exact.hpp"  // eval_exact, eval_exact_loop, grad_exact
+#include "irm_lean_plan.hpp"    // LeanFlow, LeanPhase, LeanPlan: k_lean's compile-time decisions
 #include "irm_wave.hpp"         // packed-fp32 types, DPP wave reductions, store_tile
 #include "irm_prof.hpp"         // phase profiler, IRM_STAMP / IRM_COUNT
 #include "irm_physics.hpp"      // per-waypoint physics and its reductions
 #include "irm_opt_common.hpp"   // optimiser arithmetic and problem shapes
 #include "irm_dispatch.hpp"     // dispatch_d, dispatch_t, launch_lds
-#include "irm_launch_decl.hpp"  // per-shape launcher declarations, IRM_FIX_SHAPES, IRM_EXTERN_*
+#include "irm_launch_decl.hpp"  // per-shape launcher declarations, the shape lists, IRM_EXTERN_*
 
 namespace irm {
-
-// ------------------------------------------- correctly rounded α-space maps
-// The reference's K@α@J (trajectory.py:63-65) contracts over N waypoints with
-// |α| ≈ 1e3 (singular K): a plain fp32 sum carries ~1e-4 (positions) and
-// ~1e-3 (velocities) of order-dependent noise.  Here every product of two
-// fp32 values is exact in fp64 and the N-term sum accumulates in fp64 (same
-// sequential order as oracle/irm_oracle.c), then rounds once — the result is
-// the correctly rounded fp32 value, bit-identical to the CPU oracle.  Used off
-// the hot loop: host-API evaluation and the optimiser's prologue / resyncs.
-//
-// Lane n of trajectory column block Xa (LDS, rows m = 0..N-1, stride kLd):
-//   q = fp32(fp32(K·α)[n]·J), v = fp32(fp32(dK·α)[n]·J).
-// (rs, cs: row / column strides of Xa — [row][16] LDS buffers by default, the lean kernel's
-// column-major buffers with rs = 1, cs = column stride)
-// U: K / dK rows per software-pipelined batch (8 in the prologue / epilogue; the optimiser loop's resync
-// rounds use 2, which keeps the register peak of the dual-loop / BLS instantiations low — spill-free —
-// at the cost of less latency hiding in a round that runs once per outer iteration)
-// JL: J (D×D) from Jm, an LDS copy (inside the optimiser loop, whose reads are not hoisted: the D² fp64
-// conversions of P.J hoisted out of the round loop held 2·D² VGPRs), else from P.J.  A compile-time
-// choice: a run-time select between &P.J and an LDS address takes the kernel argument's address, and the
-// compiler then copies all of KParams into scratch and reads every parameter from there (1.8 KB of
-// scratch and ≈60 scratch loads in the dual-loop / BLS rounds, round 4)
-template <int D, int U = 8, bool JL = false>
-__device__ void eval_exact(const KParams& P, const float* __restrict__ Xa, int n, float (&q)[D], float (&v)[D],
-                           const float* Kt = nullptr, const float* dKt = nullptr, int rs = kLd, int cs = 1,
-                           const float* Jm = nullptr) {
-    const float* J;
-    if constexpr (JL) J = Jm;
-    else J = P.J;
-    const int N = P.N;
-    double aq[D], av[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) aq[d] = av[d] = 0.0;
-    // wave-uniform bases and 32-bit element offsets (global loads with an SGPR base and a VGPR
-    // offset): inside the optimiser loop a per-lane 64-bit pointer would be hoisted out of the loop
-    // and held (or spilled) across every round
-    const float* kt = Kt ? Kt : P.Kt;
-    const float* dkt = dKt ? dKt : P.dKt;
-    const unsigned un = (unsigned)n, uN = (unsigned)N;
-    // K / dK rows come from L2 / HBM: software-pipelined batches of U rows (the next batch's 2U
-    // loads are in flight while this one is summed; the sum stays in the sequential order
-    // m = 0, 1, …, N−1 of the oracle)
-    const int nb = N / U;
-    int m0 = nb * U;
-    if (nb > 0) {
-        float kq[U], kv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            kq[u] = kt[(unsigned)u * uN + un];
-            kv[u] = dkt[(unsigned)u * uN + un];
-        }
-        for (int bi = 0; bi < nb; ++bi) {
-            const int mb = bi * U;
-            float nq[U], nv[U];
-            const int mn = (bi + 1 < nb) ? mb + U : mb;  // (the last batch re-reads itself: no branch)
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                nq[u] = kt[(unsigned)(mn + u) * uN + un];   // K[n][m]
-                nv[u] = dkt[(unsigned)(mn + u) * uN + un];  // dK[n][m]
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const float* xr = Xa + (mb + u) * rs;
-#pragma unroll
-                for (int d = 0; d < D; ++d) {
-                    const double x = (double)xr[d * cs];
-                    aq[d] = fma((double)kq[u], x, aq[d]);
-                    av[d] = fma((double)kv[u], x, av[d]);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                kq[u] = nq[u];
-                kv[u] = nv[u];
-            }
-        }
-    }
-    for (int m = m0; m < N; ++m) {
-        const double kq = (double)kt[(unsigned)m * uN + un], kv = (double)dkt[(unsigned)m * uN + un];
-        const float* xr = Xa + m * rs;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            const double x = (double)xr[d * cs];
-            aq[d] = fma(kq, x, aq[d]);
-            av[d] = fma(kv, x, av[d]);
-        }
-    }
-    float tq[D], tv[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        tq[d] = (float)aq[d];
-        tv[d] = (float)av[d];
-    }
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        double sq = 0.0, sv = 0.0;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            sq = fma((double)tq[d], (double)J[d * D + k], sq);
-            sv = fma((double)tv[d], (double)J[d * D + k], sv);
-        }
-        q[k] = (float)sq;
-        v[k] = (float)sv;
-    }
-}
-
-// eval_exact for one lane inside the optimiser loop (the lean kernel's resyncs at D > 3): the same sums
-// in the same order, as one loop over m whose K / dK loads run PF rows ahead, J read from LDS (Jl).
-// eval_exact's batched form kept ~80 more VGPRs live around the resync at D = 7 (its fp64 J products
-// hoisted out of the round loop, and the batch's addressing): the 7-DoF dual-loop / BLS kernels spilled.
-template <int D, int PF>
-__device__ __forceinline__ void eval_exact_loop(const KParams& P, const float* __restrict__ Xc, int ldc, int n, int N,
-                                                const float* Jl, float (&q)[D], float (&v)[D]) {
-    const unsigned un = (unsigned)n, uN = (unsigned)N;
-    double aq[D], av[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) aq[d] = av[d] = 0.0;
-    float kq = P.Kt[un], kv = P.dKt[un];
-#pragma unroll 1
-    for (int m = 0; m < N; m += PF) {
-        float nq[PF], nv[PF];
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {  // rows m+1 … m+PF (clamped: the last rows re-read row N − 1)
-            const unsigned mn = (unsigned)min(m + 1 + u, N - 1);
-            nq[u] = P.Kt[mn * uN + un];
-            nv[u] = P.dKt[mn * uN + un];
-        }
-#pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            if (PF == 1 || m + u < N) {
-#pragma unroll
-                for (int d = 0; d < D; ++d) {
-                    const double x = (double)Xc[d * ldc + m + u];
-                    aq[d] = fma((double)kq, x, aq[d]);
-                    av[d] = fma((double)kv, x, av[d]);
-                }
-            }
-            kq = nq[u];
-            kv = nv[u];
-        }
-    }
-    float tq[D], tv[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-        tq[d] = (float)aq[d];
-        tv[d] = (float)av[d];
-    }
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        // one column of J at a time: without the barrier the scheduler hoists all D² LDS reads and their fp64
-        // conversions (2·D² = 98 VGPRs at D = 7) ahead of the first product — the resync's register peak
-        __builtin_amdgcn_sched_barrier(0);
-        double sq = 0.0, sv = 0.0;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            sq = fma((double)tq[d], (double)Jl[d * D + k], sq);
-            sv = fma((double)tv[d], (double)Jl[d * D + k], sv);
-        }
-        q[k] = (float)sq;
-        v[k] = (float)sv;
-    }
-}
-
-// G[n] = (fp32(Kᵀa)[n] + fp32(dKᵀb)[n])·Jᵀ  (trajectory.py:295), the N-sums
-// in fp64 as above, the fp32 add and the D-term J product unfused in fp32
-// (the oracle's order).  Xa: a in rows 0..N-1, b in rows N..2N-1.
-template <int D>
-__device__ void grad_exact(const KParams& P, const float* __restrict__ Xa, int n, float (&G)[D]) {
-    const int N = P.N;
-    double ga[D], gb[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) ga[d] = gb[d] = 0.0;
-    const float* km = P.Km + n;
-    const float* dkm = P.dKm + n;
-    for (int m = 0; m < N; ++m) {
-        const double ka = (double)km[(size_t)m * N], kb = (double)dkm[(size_t)m * N];  // K[m][n], dK[m][n]
-        const float* xa = Xa + m * kLd;
-        const float* xb = Xa + (N + m) * kLd;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            ga[d] = fma(ka, (double)xa[d], ga[d]);
-            gb[d] = fma(kb, (double)xb[d], gb[d]);
-        }
-    }
-    float tmp[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) tmp[d] = __fadd_rn((float)ga[d], (float)gb[d]);
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        float u = 0.f;
-#pragma unroll
-        for (int l = 0; l < D; ++l) u = __fadd_rn(u, __fmul_rn(tmp[l], P.J[k * D + l]));
-        G[k] = u;
-    }
-}
 
 // Row layout of the optimiser's [a; b] / [T; V] buffers and of F: the velocity
 // half starts at row NK (= N rounded up to 16), so the position half is whole
@@ -1277,20 +1084,6 @@ __device__ __forceinline__ void ered_store_wpl(const bool (&live)[WPL], const fl
     }
 }
 
-// Control flows of the lean kernel: the GD single loop (optimizer_GD.py:68-97, the bench path), the
-// GD dual loop (optimizer_GD.py:173-232) and the BLS dual loop (optimizer_BLS.py:127-213).
-enum LeanFlow : int { LF_GD1 = 0, LF_GD2 = 1, LF_BLS = 2 };
-// Per-trajectory phase (LF_GD2 / LF_BLS): a GD step or BLS trial this round, the end of an inner
-// loop (α's exact trajectory, constraintsFulfilled, λ escalation), done.
-enum LeanPhase : int { LP_STEP = 0, LP_RESYNC = 1, LP_DONE = 2, LP_LOAD = 3 };
-// BLS line-search helpers (k_lean): when one trajectory of a workgroup is left, the first done slot
-// evaluates its next trial (lr·β₋) in the same round.  D ≤ 3, one waypoint per lane, N ≤ 128 in
-// 512-thread workgroups (or N ≤ 64): where the exchange regions fit the LDS at full occupancy.
-template <class S, int MAXT, int WPL, bool FULL, int FLOW>
-constexpr bool lean_help() {
-    return FLOW == LF_BLS && S::D <= 3 && WPL == 1 && FULL && S::kNW > 0 && (S::NK <= 64 || (S::NK <= 128 && MAXT > 256));
-}
-
 // FULL: the launch has exactly MAXT threads, so the stage-2 tiles per wave are known exactly
 // (otherwise kS2T(MAXT) bounds them for smaller launches): C7's 256-thread variant then holds 4
 // tiles of operator fragments instead of 8 (32 VGPRs) and does not spill.
@@ -1302,39 +1095,21 @@ constexpr bool lean_help() {
 // the first outer iteration's λ — followed by round 0's decision.  An index ≥ B leaves the slot done for
 // good.  No workgroup waits on another: a workgroup leaves when its flag word is empty.
 template <class S, int MAXT, int WPL, bool FULL = false, int FLOW = LF_GD1, bool QUE = false>
-__global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lean(KParams P) {
-    constexpr bool GD1 = FLOW == LF_GD1, BLS = FLOW == LF_BLS;
-    static_assert(!QUE || (FLOW != LF_GD1 && WPL == 1 && FULL && !S::kDense),
-                  "the work queue serves the dual-loop / BLS flows of the fixed shapes, one waypoint per lane");
+__global__ __launch_bounds__(MAXT, (LeanPlan<S, MAXT, WPL, FULL, FLOW, QUE>::kBlocksPerCU)) void k_lean(KParams P) {
+    // the plan: every compile-time decision of this instantiation (irm_lean_plan.hpp)
+    using PL = LeanPlan<S, MAXT, WPL, FULL, FLOW, QUE>;
     constexpr int D = S::D;
-    constexpr int S1Q = kS1Q(MAXT);
-    // stage-2 tiles per wave: all of this shape's tiles over the workgroup's waves (N = 256: 4)
-    constexpr int S2X = (S::MP / 16 + MAXT / 64 - 1) / (MAXT / 64);
-    constexpr int S2T = (FULL || S2X > kS2T(MAXT)) ? S2X : kS2T(MAXT);
-    // velocity half of stage 1 register-resident too — except in the dual-loop / BLS flows beyond C3's
-    // shape, whose extra state leaves no room (read from L2 in the dense rounds there)
-    constexpr bool RV = (MAXT > 256 || WPL > 1) && (GD1 || (D == 3 && S::NK <= 128));
-    constexpr int NWL = S::NW / WPL;  // lanes per trajectory
-    constexpr int WPTL = NWL / 64;    // waves per trajectory
-    constexpr bool VL = lean_vlds(S::NK, D, MAXT);  // V_R fragments staged in LDS (else read from L2)
-    static_assert(NWL % 64 == 0, "whole waves per trajectory");
-    static_assert(WPL == 1 || (WPL == 2 && S::kNW > 0 && S::kNW == S::NK),
-                  "two waypoints per lane: every lane's waypoints exist (N a multiple of 64)");
-    // the dense operator (DenseShape: R = N, F = L, V_R = I) runs the GD single loop with its own stages
-    constexpr bool DENSE = S::kDense;
-    static_assert(S::RP == 32 || (DENSE && GD1 && WPL == 1 && FULL),
-                  "k_lean runs at operator rank 32 (stage 2's kR24 slot skip), or the dense operator's GD loop");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const S sh(P);
     const Head H = plan_head(sh.MP, sh.RP, sh.NSPLIT, true, true);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nwaves = FULL ? MAXT / 64 : P.BT >> 6;
-    if constexpr (FULL) __builtin_assume(wave >= 0 && wave < MAXT / 64);  // tile guards fold
+    const int nwaves = PL::kWaves > 0 ? PL::kWaves : P.BT >> 6;
+    if constexpr (PL::kWaves > 0) __builtin_assume(wave >= 0 && wave < PL::kWaves);  // tile guards fold
     const int N = sh.N, TB = P.TB, RP = sh.RP, MP = sh.MP, NK = sh.NK;
-    const int t = wave / WPTL;
-    const int li = tid - t * NWL;               // this lane within its trajectory
-    const int n0 = (wave - t * WPTL) * 64;     // li of this wave's lane 0
+    const int t = wave / PL::WPTL;
+    const int li = tid - t * PL::NWL;               // this lane within its trajectory
+    const int n0 = (wave - t * PL::WPTL) * 64;     // li of this wave's lane 0
     const int tb0 = blockIdx.x * TB;
     const int ntb = min(TB, P.B - tb0);
     if (ntb <= 0) return;
@@ -1343,17 +1118,14 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     bool vl[WPL];
 #pragma unroll
     for (int j = 0; j < WPL; ++j) {
-        nn[j] = li + j * NWL;
+        nn[j] = li + j * PL::NWL;
         vl[j] = tvalid && nn[j] < N;
     }
-    // every lane of a valid trajectory holds waypoints when N fills whole waves: wherever only valid
-    // trajectories run (evaluation, gradient inputs, the α update), the waypoint guards fold away
-    constexpr bool kAllLive = S::kNW > 0 && S::kNW == S::N;
     bool wl[WPL];  // vl[j] where the trajectory is known to be valid
 #pragma unroll
-    for (int j = 0; j < WPL; ++j) wl[j] = kAllLive || nn[j] < N;
+    for (int j = 0; j < WPL; ++j) wl[j] = PL::kAllLive || nn[j] < N;
     size_t b = (size_t)(tb0 + (tvalid ? t : 0));  // (QUE: the slot's current problem)
-    const bool rec = !GD1 && !QUE && P.record_series && P.series;
+    const bool rec = !PL::GD1 && !PL::kQueue && P.record_series && P.series;
     Prof prof;
     if (tid == 0) prof.init();
 
@@ -1365,21 +1137,16 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     float* wp = smem + H.wp;
     unsigned* fw = reinterpret_cast<unsigned*>(smem + H.flags);
     float* obsL = smem + H.obs;
-    const int nsplit = sh.NSPLIT, zsplit = lean_zsplit(sh.NSPLIT, VL);
-    constexpr bool kHelp = lean_help<S, MAXT, WPL, FULL, FLOW>();
-    // helpers read t*'s α, T, V from SS: t* publishes them at the top of each helper round rather than
-    // after every accepted trial of every trajectory (C3-BLS −1 %, its faithful line −0.6 %; bit-identical)
-    constexpr bool kSSLazy = kHelp;
-    const LeanX LX = lean_extra(plan_lds(P, false, true, true).total, MP, NK, RP, nsplit, VL, D, kHelp ? MAXT : 0, BLS, DENSE);
+    const int nsplit = sh.NSPLIT, zsplit = lean_zsplit(sh.NSPLIT, PL::VL);
+    const LeanX LX = lean_extra(plan_lds(P, false, true, true).total, MP, NK, RP, nsplit, PL::VL, D, PL::kHelp ? MAXT : 0, PL::BLS, PL::DENSE);
     float* Eb = smem + LX.eb;  // e' rows [column][waypoint]
     float* Zp = smem + LX.zp;  // stage-1 partials of V_Rᵀ·e'
     float* Gb = smem + LX.gb;  // (V_R·y'')[waypoint] rows [column][waypoint]
     // b'[0], b'[N−1] of this trajectory (a copy of X's endpoint velocity rows, written with them): the B
     // operand of stage 1's endpoint MFMA (below)
     float* EPt = smem + LX.ep + t * 2 * kEpS;
-    static_assert(D <= kEpS, "endpoint rows fit their slots");
-    const float* VT = VL ? smem + LX.vt : P.VTp;
-    const float* VN = VL ? smem + LX.vn : P.VNp;
+    const float* VT = PL::VL ? smem + LX.vt : P.VTp;
+    const float* VN = PL::VL ? smem + LX.vn : P.VNp;
     // V_R fragment quad q (VT: V_Rᵀ for z, VN: V_R for G): from LDS when staged there, else from L2 through a
     // buffer descriptor — the lane's offset in one VGPR, the wave-uniform quad offset in an SGPR, so a wave's
     // batch of fragment loads holds no 64-bit address per load (at N = 256 those spilled)
@@ -1387,11 +1154,11 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     const __amdgpu_buffer_rsrc_t rVT = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.VTp), 0, (int)vbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rVN = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(P.VNp), 0, (int)vbytes, 0x00020000);
     auto vt_frag = [&](int q) -> f32x4 {
-        if constexpr (VL) return reinterpret_cast<const f32x4*>(VT)[(size_t)q * 64 + lane];
+        if constexpr (PL::VL) return reinterpret_cast<const f32x4*>(VT)[(size_t)q * 64 + lane];
         else return ld_frag(rVT, lane * 16, q * 1024);
     };
     auto vn_frag = [&](int q) -> f32x4 {
-        if constexpr (VL) return reinterpret_cast<const f32x4*>(VN)[(size_t)q * 64 + lane];
+        if constexpr (PL::VL) return reinterpret_cast<const f32x4*>(VN)[(size_t)q * 64 + lane];
         else return ld_frag(rVN, lane * 16, q * 1024);
     };
 
@@ -1408,7 +1175,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     // formed there instead of being held across the round loop (the 7-DoF dual-loop / BLS variants spilled
     // them); the 3-joint shapes have the registers, and measured 3 % slower on C3-BLS with it
     auto lnd = [](int x) {
-        if constexpr (D > 3) asm volatile("" : "+v"(x));
+        if constexpr (PL::kLaunder) asm volatile("" : "+v"(x));
         return x;
     };
     int ycl = cl;     // stage 2's Ypart column for this lane's B column (a helper round: the helper's read t*'s)
@@ -1418,9 +1185,9 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     const int kq0 = (KQa * sp1) / nsplit, kq1 = (KQa * (sp1 + 1)) / nsplit;
 
     // ----------------------------------------------------------- prologue
-    f32x4 a1[S1Q], a1v[RV ? S1Q : 1], a2[S2T * 2];
+    f32x4 a1[PL::S1Q], a1v[PL::RV ? PL::S1Q : 1], a2[PL::S2T * 2];
     auto load_ops = [&]() {
-        if constexpr (!VL) {  // (the shapes whose operands are read from L2: N = 256, 7-DoF, 256-thread)
+        if constexpr (!PL::VL) {  // (the shapes whose operands are read from L2: N = 256, 7-DoF, 256-thread)
             // buffer loads (the lane's offset in one VGPR): this also runs after each 7-DoF resync
             // (kReloadOps), where per-load 64-bit addresses held across the round loop were spilled
             const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(
@@ -1429,16 +1196,16 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                 const_cast<float*>(P.F2p), 0, (int)(frag_floats(MP, RP) * 4), 0x00020000);
             const int vo = lane * 16;
 #pragma unroll
-            for (int i = 0; i < S1Q; ++i) {
+            for (int i = 0; i < PL::S1Q; ++i) {
                 a1[i] = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (has1 && kq0 + i < kq1) a1[i] = ld_frag(r1, vo, ((tile1 * KQ1 + kq0 + i) * 64) * 16);
-                if constexpr (RV) {
+                if constexpr (PL::RV) {
                     a1v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
                     if (has1 && kq0 + i < kq1) a1v[i] = ld_frag(r1, vo, ((tile1 * KQ1 + KQa + kq0 + i) * 64) * 16);
                 }
             }
 #pragma unroll
-            for (int j = 0; j < S2T; ++j)
+            for (int j = 0; j < PL::S2T; ++j)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     a2[j * 2 + i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1449,16 +1216,16 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             const f32x4* g1 = reinterpret_cast<const f32x4*>(P.F1p);
             const f32x4* g2 = reinterpret_cast<const f32x4*>(P.F2p);
 #pragma unroll
-            for (int i = 0; i < S1Q; ++i) {
+            for (int i = 0; i < PL::S1Q; ++i) {
                 a1[i] = f32x4{0.f, 0.f, 0.f, 0.f};
                 if (has1 && kq0 + i < kq1) a1[i] = g1[((size_t)tile1 * KQ1 + kq0 + i) * 64 + lane];
-                if constexpr (RV) {
+                if constexpr (PL::RV) {
                     a1v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
                     if (has1 && kq0 + i < kq1) a1v[i] = g1[((size_t)tile1 * KQ1 + KQa + kq0 + i) * 64 + lane];
                 }
             }
 #pragma unroll
-            for (int j = 0; j < S2T; ++j)
+            for (int j = 0; j < PL::S2T; ++j)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     a2[j * 2 + i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1467,7 +1234,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                 }
         }
     };
-    if constexpr (!DENSE) load_ops();  // (DENSE: every operator fragment streamed from L2 in its stage)
+    if constexpr (!PL::DENSE) load_ops();  // (DENSE: every operator fragment streamed from L2 in its stage)
     // The endpoint velocity rows b'[0], b'[N−1] (stage 1's operator Fᵀ has zero columns there, so that a
     // sparse round can skip the velocity half) enter y'' through one more MFMA per stage-1 row tile, on
     // the split-0 units: k = 0 ↔ b'[0], k = 1 ↔ b'[N−1], k = 2, 3 zero.  A = the operator's endpoint
@@ -1482,7 +1249,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     const int epoff = (lane >> 4) < 2 ? LX.ep + (cl / D) * 2 * kEpS + (lane >> 4) * kEpS + cl % D : LX.ep0;
     // the 7-DoF BLS flow forms it again at its use (held across the round loop it was spilled)
     auto ep_at = [&]() {
-        if constexpr (BLS && D > 3 && MAXT > 256) {
+        if constexpr (PL::kEpAtUse) {
             int l = lane;
             asm volatile("" : "+v"(l));
             const int c = l & 15;
@@ -1491,7 +1258,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             return epoff;
         }
     };
-    if constexpr (VL) {
+    if constexpr (PL::VL) {
         const int nv = (int)frag_floats(RP, NK) / 4;  // = frag_floats(NK, RP) / 4
         const f32x4* gt = reinterpret_cast<const f32x4*>(P.VTp);
         const f32x4* gn = reinterpret_cast<const f32x4*>(P.VNp);
@@ -1503,7 +1270,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         }
     }
     for (int e = tid; e < 16 * lde; e += P.BT) Eb[e] = 0.f;  // no pending residual; rows ≥ N stay 0 (BLS: α rows)
-    if constexpr (BLS)
+    if constexpr (PL::BLS)
         for (int e = tid; e < kMaxTraj * kTsW; e += P.BT) smem[LX.ts + e] = 0.f;  // no slot in a line search yet
     for (int e = tid; e < kMaxTraj * 2 * kEpS + 4; e += P.BT) smem[LX.ep + e] = 0.f;  // + the zero word
     stage_obstacles(P, tb0, ntb, obsL);
@@ -1540,7 +1307,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             q[j][k] = v[j][k] = 0.f;
             al[j][k] = vl[j] ? X[nn[j] * kLd + t * D + k] : 0.f;
             // BLS: the α rows the trial stages read (written with every accepted trial)
-            if (BLS && vl[j]) Eb[(t * D + k) * lde + swz(nn[j], t * D + k)] = al[j][k];
+            if (PL::BLS && vl[j]) Eb[(t * D + k) * lde + swz(nn[j], t * D + k)] = al[j][k];
         }
         if (vl[j]) {
             eval_exact<D>(P, X + t * D, nn[j], q[j], v[j]);
@@ -1553,18 +1320,14 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     __syncthreads();
     for (int e = tid; e < MP * kLd; e += P.BT) X[e] = 0.f;
     const float* obs = obsL + (P.obs_stride ? t * obs_pitch(P.O) : 0);  // (a helper round: t*'s)
-    // 9-12 obstacles (the reference's 11): the padded table in VGPRs for the whole launch (24 floats),
-    // so the per-round evaluation does not wait on its LDS reads
-    // (and the 3-joint GD dual loop: C3 faithful 3.70 -> 3.60 ms; the BLS flow with it measured C3-BLS
-    // −0.5 % but C2 +2.7 %, not used; the 7-DoF dual loop spills with it)
-    constexpr bool OREG = GD1 || (D <= 3 && !BLS);
-    f32x4 oreg[OREG ? 6 : 1];
+    // (PL::OREG) 9-12 obstacles (the reference's 11): the padded table in VGPRs for the whole launch
+    f32x4 oreg[PL::OREG ? 6 : 1];
     const bool obs_reg = ((P.O + 3) >> 2) == 3;
 #pragma unroll
-    for (int i = 0; i < (OREG ? 6 : 1); ++i) oreg[i] = obs_reg ? reinterpret_cast<const f32x4*>(obs)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < (PL::OREG ? 6 : 1); ++i) oreg[i] = obs_reg ? reinterpret_cast<const f32x4*>(obs)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
     // replicated per-trajectory state
     float lsg = P.lsg0, ljl = P.ljl0;
-    float lr = BLS ? P.bls_lr0 : P.gd_lr[0];
+    float lr = PL::BLS ? P.bls_lr0 : P.gd_lr[0];
     float cfac = P.gd_c[0];  // GD: fp32(1 − λ_reg·lr) of the outer iteration
     float gnorm = 1.f, anorm = 0.f;  // BLS: ‖G‖ and alpha_norm of the current direction
     int outer = 0, inner = 0, trial = 0;
@@ -1581,8 +1344,8 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         // trajectories evaluate): the liveness selects of the reductions fold away
         bool lv[WPL];
 #pragma unroll
-        for (int j = 0; j < WPL; ++j) lv[j] = kAllLive || vl[j];
-        if constexpr (WPL == 2) {  // both waypoints' obstacle terms in one pass (vl[0] = vl[1] = tvalid here)
+        for (int j = 0; j < WPL; ++j) lv[j] = PL::kAllLive || vl[j];
+        if constexpr (PL::kEvalPair) {  // both waypoints' obstacle terms in one pass (vl[0] = vl[1] = tvalid here)
             if (tvalid) {
                 eval_waypoint<D, false, false, true>(P, q2[0], v2[0], obs, w[0]);
                 eval_waypoint<D, false, false, true>(P, q2[1], v2[1], obs, w[1]);
@@ -1591,7 +1354,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         }
 #pragma unroll
         for (int j = 0; j < WPL; ++j) {
-            if (WPL == 1 && lv[j]) eval_waypoint<D, false, true, true>(P, q2[j], v2[j], obs, w[j], OREG ? oreg : nullptr);  // oreg: read only when nq == 3
+            if (PL::kEvalOne && lv[j]) eval_waypoint<D, false, true, true>(P, q2[j], v2[j], obs, w[j], PL::OREG ? oreg : nullptr);  // oreg: read only when nq == 3
             cvs[j] = w[j].cv;
             const float u = fmaf(cw.c_mean, w[j].cv, cw.c_pen * (w[j].jp + w[j].jv));
             if (j == 0) {
@@ -1607,7 +1370,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             }
         }
         IRM_STAMP(6);
-        ered_store_wpl<WPL>(lv, cvs, us, tx, tn, va, ext, n0, NWL, red, wave);
+        ered_store_wpl<WPL>(lv, cvs, us, tx, tn, va, ext, n0, PL::NWL, red, wave);
 #pragma unroll
         for (int j = 0; j < WPL; ++j) {
             const int n = nn[j];
@@ -1628,22 +1391,15 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         float nl, tx, tn, va, a0, b0, a1, b1;
         int idx;
     };
-    // Latency-hiding load batches (finalize's records and start/goal terms, stage 2's split-K partial
-    // sums, the z unit's operands) hold more values live at once: stage 2's and the z unit's only for
-    // N <= 128, where they fit without spills; at N = 256 (four splits, eight z ranges) they pushed the
-    // spill-free GD single-loop variants into scratch (C5: 14 spilled VGPRs)
-    // finalize's batch: fixed shapes with one waypoint per lane (C4's two-waypoints-per-lane kernel, one
-    // wave record per trajectory, measured 2 % slower with it; C5 / C7 1.5-2 % faster)
-    constexpr bool kLatF = S::kNW > 0 && WPL == 1;
-    constexpr bool kLatS = S::kNW > 0 && S::NK <= 128;   // stage 2's and the z unit's: N <= 128
+    // (PL::kLatF: the latency-hiding batch of the records and start/goal terms, below)
     auto finalize = [&](float lsg_e, int ft) {  // ft: the trajectory slot whose records are read
-        if constexpr (!kLatF) {
-            const float* r0 = red + (ft * WPTL) * 8;
+        if constexpr (!PL::kLatF) {
+            const float* r0 = red + (ft * PL::WPTL) * 8;
             float cmax = r0[0];
             int cidx = __float_as_int(r0[1]);
             float usum = r0[2], tx = r0[3], tn = r0[4], va = r0[5];
-            for (int ww = 1; ww < WPTL; ++ww) {
-                const float* rw = red + (ft * WPTL + ww) * 8;
+            for (int ww = 1; ww < PL::WPTL; ++ww) {
+                const float* rw = red + (ft * PL::WPTL + ww) * 8;
                 amax_step(cmax, cidx, rw[0], __float_as_int(rw[1]));
                 usum += rw[2];
                 tx = fmaxf(tx, rw[3]);
@@ -1666,11 +1422,11 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         }
         // every wave record and the start/goal terms are read before the first use (one LDS round trip;
         // the argmax merge as selects, so no read is sunk into a branch)
-        float rr[WPTL][6], sgr[4];
+        float rr[PL::WPTL][6], sgr[4];
 #pragma unroll
-        for (int ww = 0; ww < WPTL; ++ww)
+        for (int ww = 0; ww < PL::WPTL; ++ww)
 #pragma unroll
-            for (int e = 0; e < 6; ++e) rr[ww][e] = red[(ft * WPTL + ww) * 8 + e];
+            for (int e = 0; e < 6; ++e) rr[ww][e] = red[(ft * PL::WPTL + ww) * 8 + e];
 #pragma unroll
         for (int e = 0; e < 4; ++e) sgr[e] = sg[ft * 4 + e];
         __builtin_amdgcn_sched_barrier(0);
@@ -1678,7 +1434,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         int cidx = __float_as_int(rr[0][1]);
         float usum = rr[0][2], tx = rr[0][3], tn = rr[0][4], va = rr[0][5];
 #pragma unroll
-        for (int ww = 1; ww < WPTL; ++ww) {
+        for (int ww = 1; ww < PL::WPTL; ++ww) {
             const float ov = rr[ww][0];
             const int oi = __float_as_int(rr[ww][1]);
             const bool take = (ov > cmax) | ((ov == cmax) & (oi < cidx));  // amax_step (no short-circuit branch)
@@ -1744,37 +1500,22 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         }
         return bfar != 0ull;
     };
-    // GD single loop, fixed-shape launches: stage 1's B operand (both halves; the velocity half is used
-    // in dense rounds only) is read at the top of the round, before the flag word (X was written before
-    // the previous barrier), so the flag and operand LDS round trips overlap; same values, same MFMA
-    // order (bit-identical, tools/sched_check.py).  C3 0.769 -> 0.759 ms; the position half alone: no gain.
-    constexpr bool kFix1 = S::KQU > 0 && S::KQU <= S1Q;
-    constexpr int KQU1 = kFix1 ? S::KQU : S1Q;
-    // (the GD dual loop with the same prefetch: 4.33 -> 4.47 ms, 242 VGPRs there; not used)
-    constexpr bool kPre1 = GD1 && FULL && kFix1;
-    constexpr bool kPreW = kPre1 && RV;
-    // C3's kernel (N = 128 in 512-thread workgroups): the round's LDS reads issued in the order of their use —
-    // the round top and the decision, below.  Issue order only: same loads, same MFMAs, same order per chain
-    // (bit-identical, tools/sched_check.py).  Alternating 300-step bench runs against the parent build: stage
-    // 1's order alone −0.6 %, the G words alone −0.7 %, both −1.6 % (profiles/gd1_top_ab.txt); the z unit's
-    // e' quads read at the round top as well measured +0.8 % alone and is not done
-    constexpr bool kTopC3 = kPreW && D <= 3 && WPL == 1 && MAXT > 256 && WPTL > 1 && kLatS;
-    constexpr bool kS1Ord = kTopC3;  // flag word first, stage 1's operands in use order
-    constexpr bool kGFin = kTopC3;   // the α update's G words read with finalize's records
-    auto stage1_load = [&](f32x4 (&bv)[KQU1], f32x4 (&bw)[KQU1], float& bep) {
+    // stage 1's B operand read at the top of the round (PL::kPre1, PL::kPreW: with the velocity half), in
+    // the order of its use (PL::kS1Ord)
+    auto stage1_load = [&](f32x4 (&bv)[PL::KQU1], f32x4 (&bw)[PL::KQU1], float& bep) {
         const float* xl = X + cl * ldx + r4x;
-        if constexpr (kS1Ord) {
+        if constexpr (PL::kS1Ord) {
             // (has1 waves) the endpoint word, then the position quads in the order stage 1's chains consume
             // them, then the velocity quads: LDS returns in order, so each MFMA group waits for its own quad
             bep = smem[epoff];
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int i = 0; i < KQU1; ++i) {
+            for (int i = 0; i < PL::KQU1; ++i) {
                 bv[i] = *reinterpret_cast<const f32x4*>(xl + (kq0 + i) * 16);
                 __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
-            for (int i = 0; i < KQU1; ++i) {
+            for (int i = 0; i < PL::KQU1; ++i) {
                 bw[i] = *reinterpret_cast<const f32x4*>(xl + (KQa + kq0 + i) * 16);
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -1782,32 +1523,30 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         }
         if (has1) {  // wave-uniform
 #pragma unroll
-            for (int i = 0; i < KQU1; ++i) {
+            for (int i = 0; i < PL::KQU1; ++i) {
                 bv[i] = *reinterpret_cast<const f32x4*>(xl + (kq0 + i) * 16);
-                if constexpr (kPreW) bw[i] = *reinterpret_cast<const f32x4*>(xl + (KQa + kq0 + i) * 16);
+                if constexpr (PL::kPreW) bw[i] = *reinterpret_cast<const f32x4*>(xl + (KQa + kq0 + i) * 16);
             }
             bep = smem[epoff];  // (a valid word on every stage-1 wave; used on the endpoint waves)
         }
     };
     // Ypart[sp] = Fᵀ·[a'; b'] over this wave's unit (+ the endpoint rows' MFMA on the split-0 units)
-    auto stage1 = [&](bool full, const f32x4 (&pre)[KQU1], const f32x4 (&prew)[KQU1], float prep) {
+    auto stage1 = [&](bool full, const f32x4 (&pre)[PL::KQU1], const f32x4 (&prew)[PL::KQU1], float prep) {
         if (!has1) return;
         const float* xl = X + cl * ldx + r4x;
-        constexpr bool kFix = kFix1;
-        constexpr int KQU = KQU1;
-        auto in = [&](int i) { return kFix ? i < KQU : kq0 + i < kq1; };
+        auto in = [&](int i) { return PL::kFix1 ? i < PL::KQU1 : kq0 + i < kq1; };
         const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-        f32x4 bv[KQU], bw[RV ? KQU : 1];
+        f32x4 bv[PL::KQU1], bw[PL::RV ? PL::KQU1 : 1];
 #pragma unroll
-        for (int i = 0; i < KQU; ++i) {
-            if constexpr (kPre1) bv[i] = pre[i];
+        for (int i = 0; i < PL::KQU1; ++i) {
+            if constexpr (PL::kPre1) bv[i] = pre[i];
             else bv[i] = in(i) ? *reinterpret_cast<const f32x4*>(xl + (kq0 + i) * 16) : z4;
         }
-        if constexpr (RV) {
+        if constexpr (PL::RV) {
             if (full) {
 #pragma unroll
-                for (int i = 0; i < KQU; ++i) {
-                    if constexpr (kPreW) bw[i] = prew[i];
+                for (int i = 0; i < PL::KQU1; ++i) {
+                    if constexpr (PL::kPreW) bw[i] = prew[i];
                     else bw[i] = in(i) ? *reinterpret_cast<const f32x4*>(xl + (KQa + kq0 + i) * 16) : z4;
                 }
             }
@@ -1815,29 +1554,29 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         f32x4 acc0 = z4, acc1 = z4;
         // fixed shapes: the second chain's first product is the endpoint MFMA's successor or starts from
         // zero itself (one MFMA result either way: no zeroed accumulator on the non-endpoint waves)
-        if constexpr (kFix) {
+        if constexpr (PL::kFix1) {
             if (hasep) {
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(aep, kPre1 ? prep : smem[ep_at()], z4, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(aep, PL::kPre1 ? prep : smem[ep_at()], z4, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[0][1], bv[0][1], acc1, 0, 0, 0);
             } else {
                 acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[0][1], bv[0][1], z4, 0, 0, 0);
             }
         } else if (hasep) {
-            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(aep, kPre1 ? prep : smem[ep_at()], acc1, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(aep, PL::kPre1 ? prep : smem[ep_at()], acc1, 0, 0, 0);
         }
 #pragma unroll
-        for (int i = 0; i < KQU; ++i) {
+        for (int i = 0; i < PL::KQU1; ++i) {
             if (in(i)) {
                 acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i][0], bv[i][0], acc0, 0, 0, 0);
-                if (!kFix || i > 0) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i][1], bv[i][1], acc1, 0, 0, 0);
+                if (!PL::kFix1 || i > 0) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i][1], bv[i][1], acc1, 0, 0, 0);
                 acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i][2], bv[i][2], acc0, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i][3], bv[i][3], acc1, 0, 0, 0);
             }
         }
         if (full) {
-            if constexpr (RV) {
+            if constexpr (PL::RV) {
 #pragma unroll
-                for (int i = 0; i < KQU; ++i) {
+                for (int i = 0; i < PL::KQU1; ++i) {
                     if (in(i)) {
                         acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1v[i][0], bw[i][0], acc0, 0, 0, 0);
                         acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1v[i][1], bw[i][1], acc1, 0, 0, 0);
@@ -1845,7 +1584,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                         acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1v[i][3], bw[i][3], acc1, 0, 0, 0);
                     }
                 }
-            } else if constexpr (!VL) {
+            } else if constexpr (!PL::VL) {
                 // (buffer loads: the lane's offset in one VGPR, no 64-bit address held across the round loop)
                 const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(
                     const_cast<float*>(P.F1p), 0, (int)(frag_floats(RP, MP) * 4), 0x00020000);
@@ -1876,64 +1615,49 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     // 1e-7 per step, so only V_R's first row tile is applied (half the MFMAs of rank 32; Zp rows 16-31
     // stay zero).  zsplit k-ranges over the waves from the top down (C3: waves 4-7, idle in the Fᵀ
     // stage), operator from LDS / L2.
-    // FULL launches of a fixed shape with an even split: the unit's operator and e' loads are issued
-    // up front (one wait), then the MFMAs — the same accumulation order as the loop below
-    constexpr int kZS = lean_zsplit(S::NSPLIT, VL), kKQa = S::NK / 16;
-    constexpr bool kZFix = FULL && S::kNW > 0 && kKQa % kZS == 0 && kZS <= MAXT / 64;
-    constexpr int kKQZ = kZFix ? kKQa / kZS : 1;
-    constexpr int kMTG = S::NK / 16, kGT = (kMTG + MAXT / 64 - 1) / (MAXT / 64);
-    constexpr bool kS2Fix = FULL && S::kNW > 0;
-    // GD flows of the fixed shapes: the z unit's V_Rᵀ fragments and the G tiles' V_R fragments are the same
-    // every round — held in VGPRs for the launch instead of re-read from LDS / L2 each round
-    // (C3 faithful 3.93 -> 3.75 ms, C3 even; from L2 too: C7 1.33 -> 1.27 ms, C7 faithful 7.52 -> 7.30 ms,
-    // C5 1.405 -> 1.326 ms, C4 even; bit-identical.  Not the 7-DoF N = 256 dual loop / 256-thread
-    // variants, which spill with them)
-    constexpr bool kVReg = !BLS && !DENSE && kZFix && kS2Fix && (VL || !(D > 3 && S::NK > 128) || (GD1 && MAXT > 256));
-    // otherwise (C5's dual loop) the z unit's V_Rᵀ fragments are loaded at the round's top, so their L2
-    // latency passes under stage 1 instead of holding the z waves at the stage-1 barrier
-    // (C5 faithful −1.4 %, C4 even; bit-identical)
-    constexpr bool kZPre = !BLS && !DENSE && kZFix && !kVReg;
-    f32x4 vtR[kVReg ? kKQZ : 1], vnR[kVReg ? kGT : 1][2];
-    if constexpr (kVReg) {
+    // PL::kZFix (FULL launches of a fixed shape with an even split): the unit's operator and e' loads are
+    // issued up front (one wait), then the MFMAs — the same accumulation order as the loop below.  The V_Rᵀ /
+    // V_R fragments are held in VGPRs for the launch (PL::kVReg) or loaded at the round's top (PL::kZPre)
+    f32x4 vtR[PL::kVReg ? PL::kKQZ : 1], vnR[PL::kVReg ? PL::kGT : 1][2];
+    if constexpr (PL::kVReg) {
         const int sp = nwaves - 1 - wave;
 #pragma unroll
-        for (int i = 0; i < kKQZ; ++i) vtR[i] = sp < kZS ? vt_frag(sp * kKQZ + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int i = 0; i < PL::kKQZ; ++i) vtR[i] = sp < PL::kZS ? vt_frag(sp * PL::kKQZ + i) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int g = 0; g < kGT; ++g) {
+        for (int g = 0; g < PL::kGT; ++g) {
             const int u = nwaves - 1 - wave + g * nwaves;
             vnR[g][0] = vnR[g][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (u < kMTG) {
+            if (u < PL::kMTG) {
                 vnR[g][0] = vn_frag(u * KQ2);
                 vnR[g][1] = vn_frag(u * KQ2 + 1);
             }
         }
     }
-    auto zpre_load = [&](f32x4 (&zp)[kZPre ? kKQZ : 1]) {
-        if constexpr (kZPre) {
+    auto zpre_load = [&](f32x4 (&zp)[PL::kZPre ? PL::kKQZ : 1]) {
+        if constexpr (PL::kZPre) {
             const int sp = nwaves - 1 - wave;
-            if (sp < kZS) {
+            if (sp < PL::kZS) {
 #pragma unroll
-                for (int i = 0; i < kKQZ; ++i) zp[i] = vt_frag(sp * kKQZ + i);
+                for (int i = 0; i < PL::kKQZ; ++i) zp[i] = vt_frag(sp * PL::kKQZ + i);
             }
         }
     };
-    auto stage1z = [&](const f32x4 (&zp)[kZPre ? kKQZ : 1]) {
+    auto stage1z = [&](const f32x4 (&zp)[PL::kZPre ? PL::kKQZ : 1]) {
         const float* el = Eb + cl * lde + r4x;
-        if constexpr (kZFix) {
-            constexpr int KQZ = kKQZ;
+        if constexpr (PL::kZFix) {
             const int sp = nwaves - 1 - wave;
-            if (sp >= kZS) return;
-            f32x4 a[KQZ], bb[KQZ];
+            if (sp >= PL::kZS) return;
+            f32x4 a[PL::kKQZ], bb[PL::kKQZ];
 #pragma unroll
-            for (int i = 0; i < KQZ; ++i) {
-                if constexpr (kZPre) a[i] = zp[i];
-                else a[i] = kVReg ? vtR[i] : vt_frag(sp * KQZ + i);
-                bb[i] = *reinterpret_cast<const f32x4*>(el + (sp * KQZ + i) * 16);
+            for (int i = 0; i < PL::kKQZ; ++i) {
+                if constexpr (PL::kZPre) a[i] = zp[i];
+                else a[i] = PL::kVReg ? vtR[i] : vt_frag(sp * PL::kKQZ + i);
+                bb[i] = *reinterpret_cast<const f32x4*>(el + (sp * PL::kKQZ + i) * 16);
             }
-            if constexpr (kLatS) __builtin_amdgcn_sched_barrier(0);  // all loads in flight before the first MFMA
+            if constexpr (PL::kLatS) __builtin_amdgcn_sched_barrier(0);  // all loads in flight before the first MFMA
             f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int i = 0; i < KQZ; ++i) {
+            for (int i = 0; i < PL::kKQZ; ++i) {
                 acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][0], bb[i][0], acc0, 0, 0, 0);
                 acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][1], bb[i][1], acc1, 0, 0, 0);
                 acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][2], bb[i][2], acc0, 0, 0, 0);
@@ -1963,31 +1687,23 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     // The α iterate uses G (rank 24, the reference's gradient to fp32 resolution); the waypoint state
     // follows the rank-16 direction, off L·α·J by ≲ 1.5e-7 of a step per step (the one-residual lag
     // below is 1e-4), and every inner-loop end replaces it by eval_exact(α).
-    // FULL launches of a fixed shape: the G tiles of a wave are known at compile time; their operator
-    // fragments are loaded with the partial sums and their MFMAs interleave with the F tiles' (same
-    // accumulation order per tile as the general form below)
-    constexpr bool kS2Batch = kS2Fix && kLatS;  // stage 2's partial sums read in one batch
+    // FULL launches of a fixed shape (PL::kS2Fix): the G tiles of a wave are known at compile time; their
+    // operator fragments are loaded with the partial sums (in one batch: PL::kS2Batch) and their MFMAs
+    // interleave with the F tiles' (same accumulation order per tile as the general form below)
     // WF: the F tiles (dP, with the residual z folded in), WG: the G tiles (Gb).  The GD flows run both in
     // one pass; the BLS flow runs G in the rounds with a new gradient input and F in every trial round
     // (its trial's own residual folded in, so the direction is the trial iterate's)
-    // the GD single loop's G tiles issued after the stage-2 barrier (their MFMAs under the update and
-    // evaluation; C3 -2.0 %, bit-identical)
-    // (the same in every non-BLS flow measured neutral on C4, C5, C7 and +1.2 % on the 3-joint GD dual loop,
-    // profiles/r05_glate_ab.txt: not kept)
-    // (WPTL > 1 only: glate_tiles' waves write G rows of trajectories they do not own, and with one wave per
-    // trajectory — N ≤ 64 — only a wave barrier would sit between that write and the owner's read: a race)
-    constexpr bool kGLate = GD1 && D <= 3 && kS2Fix && kS2Batch && WPTL > 1;
     f32x4 glY0 = f32x4{0.f, 0.f, 0.f, 0.f}, glY1 = f32x4{0.f, 0.f, 0.f, 0.f};
     // (kGLate) the G tiles, issued right after the stage-2 barrier: their MFMAs under the update /
     // evaluation's VALU work; Gb is read after the evaluation's barrier (the decision).  Issued after the
     // update instead, C3 measured +5.7 %
     auto glate_tiles = [&]() {
 #pragma unroll
-        for (int g = 0; g < kGT; ++g) {
+        for (int g = 0; g < PL::kGT; ++g) {
             const int u = nwaves - 1 - wave + g * nwaves;
-            if (u < kMTG) {
-                const f32x4 g0 = kVReg ? vnR[g][0] : vn_frag(u * KQ2);
-                const f32x4 g1 = kVReg ? vnR[g][1] : vn_frag(u * KQ2 + 1);
+            if (u < PL::kMTG) {
+                const f32x4 g0 = PL::kVReg ? vnR[g][0] : vn_frag(u * KQ2);
+                const f32x4 g1 = PL::kVReg ? vnR[g][1] : vn_frag(u * KQ2 + 1);
                 f32x4 ag = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int m = 0; m < 4; ++m) ag = __builtin_amdgcn_mfma_f32_16x16x4f32(g0[m], glY0[m], ag, 0, 0, 0);
@@ -1999,23 +1715,23 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     };
     auto stage2f = [&](auto WFc, auto WGc) {
         constexpr bool WF = decltype(WFc)::value, WG = decltype(WGc)::value;
-        f32x4 acc[S2T];
+        f32x4 acc[PL::S2T];
 #pragma unroll
-        for (int j = 0; j < S2T; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        f32x4 ga[kS2Fix ? kGT : 1][2];
-        if constexpr (kS2Fix && WG) {
+        for (int j = 0; j < PL::S2T; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 ga[PL::kS2Fix ? PL::kGT : 1][2];
+        if constexpr (PL::kS2Fix && WG) {
 #pragma unroll
-            for (int g = 0; g < kGT; ++g) {
+            for (int g = 0; g < PL::kGT; ++g) {
                 const int u = nwaves - 1 - wave + g * nwaves;
                 ga[g][0] = ga[g][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (u < kMTG) {
-                    ga[g][0] = kVReg ? vnR[g][0] : vn_frag(u * KQ2);
-                    ga[g][1] = kVReg ? vnR[g][1] : vn_frag(u * KQ2 + 1);
+                if (u < PL::kMTG) {
+                    ga[g][0] = PL::kVReg ? vnR[g][0] : vn_frag(u * KQ2);
+                    ga[g][1] = PL::kVReg ? vnR[g][1] : vn_frag(u * KQ2 + 1);
                 }
             }
         }
         f32x4 by[2], bt[2];
-        if constexpr (kS2Batch) {
+        if constexpr (PL::kS2Batch) {
             // every split-K partial of y'' and z is read before the first sum (one LDS round trip; the
             // machine scheduler otherwise reuses one register quad for the reads and waits after each,
             // seven round trips per round); same sums in the same order as the general form below
@@ -2023,19 +1739,19 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             // (read as whole quads: the swizzled layout is conflict-free for ds_read_b128, not for the
             // b64 reads the compiler narrows these to — SQ_LDS_BANK_CONFLICT 0.8 M -> 4.1 M cycles)
             constexpr int NS = S::NSPLIT;
-            f32x4 yp[NS], zq[kZS], yq[NS];
+            f32x4 yp[NS], zq[PL::kZS], yq[NS];
 #pragma unroll
             for (int sp = 0; sp < NS; ++sp) {
                 yp[sp] = *reinterpret_cast<const f32x4*>(Ypart + (sp * 16 + ycl) * ldy + r4y);
                 yq[sp] = *reinterpret_cast<const f32x4*>(Ypart + (sp * 16 + ycl) * ldy + 16 + r4y);
             }
 #pragma unroll
-            for (int sp = 0; sp < (WF ? kZS : 0); ++sp) zq[sp] = *reinterpret_cast<const f32x4*>(Zp + (sp * 16 + cl) * ldy + r4x);
+            for (int sp = 0; sp < (WF ? PL::kZS : 0); ++sp) zq[sp] = *reinterpret_cast<const f32x4*>(Zp + (sp * 16 + cl) * ldy + r4x);
             // every quad stays whole (no narrowing, no register reuse of its unused half while in flight)
 #pragma unroll
             for (int sp = 0; sp < NS; ++sp) asm volatile("" ::"v"(yq[sp]));
 #pragma unroll
-            for (int g = 0; g < (WG ? kGT : 0); ++g) asm volatile("" ::"v"(ga[g][1]));
+            for (int g = 0; g < (WG ? PL::kGT : 0); ++g) asm volatile("" ::"v"(ga[g][1]));
             __builtin_amdgcn_sched_barrier(0);
             // the sums start from the first partial (not from +0: four adds fewer per quad; a partial
             // of −0 stays −0, which changes no MFMA product sum that is not exactly zero)
@@ -2046,20 +1762,20 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                 by[0] += yp[sp];
                 b1 += f32x2{yq[sp].x, yq[sp].y};
             }
-            if constexpr (kS2Fix && WF && WG) {
+            if constexpr (PL::kS2Fix && WF && WG) {
                 // the G tiles first, on y'' alone (read first), while the z partials are still in flight;
                 // then the F tiles on y'' + z — each tile's MFMA chain unchanged (bit-identical; C3 −0.4 %,
                 // C3 faithful −1 %)
                 const f32x4 by1 = f32x4{b1.x, b1.y, 0.f, 0.f};
-                f32x4 ag[kGT];
-                if constexpr (kGLate) {
+                f32x4 ag[PL::kGT];
+                if constexpr (PL::kGLate) {
                     glY0 = by[0];
                     glY1 = by1;
                 }
 #pragma unroll
-                for (int g = 0; g < kGT; ++g) {
+                for (int g = 0; g < PL::kGT; ++g) {
                     ag[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (!kGLate && nwaves - 1 - wave + g * nwaves < kMTG) {
+                    if (!PL::kGLate && nwaves - 1 - wave + g * nwaves < PL::kMTG) {
 #pragma unroll
                         for (int m = 0; m < 4; ++m) ag[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(ga[g][0][m], by[0][m], ag[g], 0, 0, 0);
 #pragma unroll
@@ -2069,29 +1785,29 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                 __builtin_amdgcn_sched_barrier(0);  // (the z sums after the G chain: it must not wait for them)
                 f32x4 bz = zq[0];
 #pragma unroll
-                for (int sp = 1; sp < kZS; ++sp) bz += zq[sp];
+                for (int sp = 1; sp < PL::kZS; ++sp) bz += zq[sp];
                 const f32x4 b0 = by[0] + bz;
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
 #pragma unroll
-                    for (int j = 0; j < S2T; ++j)
+                    for (int j = 0; j < PL::S2T; ++j)
                         if (wave + j * nwaves < MT2)
                             acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a2[j * 2][m], b0[m], acc[j], 0, 0, 0);
 #pragma unroll
-                for (int j = 0; j < S2T; ++j)
+                for (int j = 0; j < PL::S2T; ++j)
                     if (wave + j * nwaves < MT2)
                         *reinterpret_cast<f32x4*>(dP + cl * ldx + (wave + j * nwaves) * 16 + r4x) = acc[j];
 #pragma unroll
-                for (int g = 0; g < kGT; ++g) {
+                for (int g = 0; g < PL::kGT; ++g) {
                     const int u = nwaves - 1 - wave + g * nwaves;
-                    if (!kGLate && u < kMTG) *reinterpret_cast<f32x4*>(Gb + cl * lde + u * 16 + r4x) = ag[g];
+                    if (!PL::kGLate && u < PL::kMTG) *reinterpret_cast<f32x4*>(Gb + cl * lde + u * 16 + r4x) = ag[g];
                 }
                 return;
             }
             if constexpr (WF) {
                 f32x4 bz = zq[0];
 #pragma unroll
-                for (int sp = 1; sp < kZS; ++sp) bz += zq[sp];
+                for (int sp = 1; sp < PL::kZS; ++sp) bz += zq[sp];
                 bt[0] = by[0] + bz;
             } else {
                 bt[0] = by[0];
@@ -2099,7 +1815,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             by[1] = bt[1] = f32x4{b1.x, b1.y, 0.f, 0.f};
         }
 #pragma unroll
-        for (int i = 0; i < (kS2Batch ? 0 : 2); ++i) {
+        for (int i = 0; i < (PL::kS2Batch ? 0 : 2); ++i) {
             by[i] = bt[i] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (i < KQ2) {
                 f32x4 bz = {0.f, 0.f, 0.f, 0.f};
@@ -2114,40 +1830,40 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         }
         // the waypoint direction F·(y'' + z) at rank 16: F_r·y''_r ∝ σ_r², (σ_16/σ_0)² ≈ 1.5e-7 (N = 128),
         // i.e. the fp32 rounding level of the direction itself (kR16F)
-        if constexpr (kS2Fix) {
-            f32x4 ag[kGT];
+        if constexpr (PL::kS2Fix) {
+            f32x4 ag[PL::kGT];
 #pragma unroll
-            for (int g = 0; g < kGT; ++g) ag[g] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int g = 0; g < PL::kGT; ++g) ag[g] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
 #pragma unroll
-                for (int j = 0; j < (WF ? S2T : 0); ++j)
+                for (int j = 0; j < (WF ? PL::S2T : 0); ++j)
                     if (wave + j * nwaves < MT2)
                         acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a2[j * 2][m], bt[0][m], acc[j], 0, 0, 0);
 #pragma unroll
-                for (int g = 0; g < (WG ? kGT : 0); ++g)
-                    if (nwaves - 1 - wave + g * nwaves < kMTG)
+                for (int g = 0; g < (WG ? PL::kGT : 0); ++g)
+                    if (nwaves - 1 - wave + g * nwaves < PL::kMTG)
                         ag[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(ga[g][0][m], by[0][m], ag[g], 0, 0, 0);
             }
 #pragma unroll
             for (int m = 0; m < 2; ++m)  // kR24
 #pragma unroll
-                for (int g = 0; g < (WG ? kGT : 0); ++g)
-                    if (nwaves - 1 - wave + g * nwaves < kMTG)
+                for (int g = 0; g < (WG ? PL::kGT : 0); ++g)
+                    if (nwaves - 1 - wave + g * nwaves < PL::kMTG)
                         ag[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(ga[g][1][m], by[1][m], ag[g], 0, 0, 0);
 #pragma unroll
-            for (int j = 0; j < (WF ? S2T : 0); ++j)
+            for (int j = 0; j < (WF ? PL::S2T : 0); ++j)
                 if (wave + j * nwaves < MT2)
                     *reinterpret_cast<f32x4*>(dP + cl * ldx + (wave + j * nwaves) * 16 + r4x) = acc[j];
 #pragma unroll
-            for (int g = 0; g < (WG ? kGT : 0); ++g) {
+            for (int g = 0; g < (WG ? PL::kGT : 0); ++g) {
                 const int u = nwaves - 1 - wave + g * nwaves;
-                if (u < kMTG) *reinterpret_cast<f32x4*>(Gb + cl * lde + u * 16 + r4x) = ag[g];
+                if (u < PL::kMTG) *reinterpret_cast<f32x4*>(Gb + cl * lde + u * 16 + r4x) = ag[g];
             }
             return;
         }
 #pragma unroll
-        for (int j = 0; j < (WF ? S2T : 0); ++j) {
+        for (int j = 0; j < (WF ? PL::S2T : 0); ++j) {
             if (wave + j * nwaves < MT2) {
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
@@ -2155,7 +1871,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             }
         }
 #pragma unroll
-        for (int j = 0; j < (WF ? S2T : 0); ++j) {
+        for (int j = 0; j < (WF ? PL::S2T : 0); ++j) {
             if (wave + j * nwaves < MT2)
                 *reinterpret_cast<f32x4*>(dP + cl * ldx + (wave + j * nwaves) * 16 + r4x) = acc[j];
         }
@@ -2185,28 +1901,20 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     // G / α rows → barrier → F tiles → barrier.  Every column's trial is its trajectory's current one (lr
     // from TS); a helper's columns take t*'s next (lr·β₋): ycl is the column whose y'', G and α the
     // lane's column reads.
-    constexpr int kNZP = lean_bls_nzp(S::kNW > 0 ? S::NK : 256);
     const int nzp = min(nwaves, MTG);  // z partials (one per G-tile wave)
-    // (fixed shapes up to N = 128: at N = 256 the batch's per-tile operands — four tiles per wave at 256
-    // threads — pushed the BLS variants into scratch; those take the per-tile loop, same sums in the same order)
-    constexpr bool kBFix = FULL && S::kNW > 0 && S::NK <= 128;
-    constexpr int kNZc = kBFix ? (MAXT / 64 < S::NK / 16 ? MAXT / 64 : S::NK / 16) : 1;
-    static_assert(!BLS || !kBFix || kNZc <= kNZP, "z partials fit their region");
+    // (PL::kBFix, fixed shapes up to N = 128: the tiles' operands in one batch; else the per-tile loop)
     float* Ab = smem + LX.eb;    // BLS: α rows [column][waypoint] (Eb's place)
     float* Ajb = smem + LX.aj;   // BLS: the round's trial iterate α_j, rows [column][waypoint]
     float* Zq = smem + LX.zp;    // BLS: z partials, quad-major
     float* TS = smem + LX.ts;    // BLS: per-slot lr, ‖G‖, in-a-line-search flag
-    // V_R staged in LDS: the G-tile waves' V_R / V_Rᵀ fragments held in VGPRs for the launch (as kVReg)
-    constexpr int kTB = kBFix ? (S::NK / 16 + MAXT / 64 - 1) / (MAXT / 64) : 1;  // tiles per wave
-    // (C3-BLS faithful 7.21 -> 7.17 ms, C3-BLS 1.426 -> 1.419 ms; bit-identical)
-    constexpr bool kVRegB = BLS && VL && kBFix;
-    f32x4 bvt[kVRegB ? kTB : 1], bvn[kVRegB ? kTB : 1][2];
-    if constexpr (kVRegB) {
+    // PL::kVRegB (V_R staged in LDS): the G-tile waves' V_R / V_Rᵀ fragments held in VGPRs for the launch
+    f32x4 bvt[PL::kVRegB ? PL::kTB : 1], bvn[PL::kVRegB ? PL::kTB : 1][2];
+    if constexpr (PL::kVRegB) {
 #pragma unroll
-        for (int g = 0; g < kTB; ++g) {
-            const int u = nwaves - 1 - wave + g * (MAXT / 64);
+        for (int g = 0; g < PL::kTB; ++g) {
+            const int u = nwaves - 1 - wave + g * PL::kDW;
             bvt[g] = bvn[g][0] = bvn[g][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (u < S::NK / 16) {
+            if (u < PL::kMTG) {
                 bvt[g] = vt_frag(u);
                 bvn[g][0] = vn_frag(u * KQ2);
                 bvn[g][1] = vn_frag(u * KQ2 + 1);
@@ -2221,20 +1929,19 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         // the slot's trial scalars, read with the round's first LDS batch
         const float lrs = TS[sc * kTsW + 0];
         const bool act = TS[sc * kTsW + 2] != 0.f;  // (other slots: no residual)
-        constexpr int kT = kBFix ? (S::NK / 16 + MAXT / 64 - 1) / (MAXT / 64) : 1;  // tiles per wave (fixed)
-        const int ntl = kBFix ? kT : (MTG - pz + nwaves - 1) / nwaves;
-        f32x4 Gt[kBFix ? kT : 1];
+        const int ntl = PL::kBFix ? PL::kTB : (MTG - pz + nwaves - 1) / nwaves;
+        f32x4 Gt[PL::kBFix ? PL::kTB : 1];
         // fixed shapes: every tile's α rows and V_Rᵀ fragment (and, continuing a search, its stored G) read
         // in the round's first LDS batch
-        f32x4 Ap[kBFix ? kT : 1], Vp[kBFix ? kT : 1];
-        if constexpr (kBFix) {
+        f32x4 Ap[PL::kBFix ? PL::kTB : 1], Vp[PL::kBFix ? PL::kTB : 1];
+        if constexpr (PL::kBFix) {
 #pragma unroll
-            for (int g = 0; g < kT; ++g) {
-                const int u = pz + g * (MAXT / 64);
+            for (int g = 0; g < PL::kTB; ++g) {
+                const int u = pz + g * PL::kDW;
                 Ap[g] = Vp[g] = Gt[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (u < S::NK / 16) {
+                if (u < PL::kMTG) {
                     Ap[g] = *reinterpret_cast<const f32x4*>(Ab + ycl * lde + u * 16 + r4y);
-                    Vp[g] = kVRegB ? bvt[g] : vt_frag(u);
+                    Vp[g] = PL::kVRegB ? bvt[g] : vt_frag(u);
                     if constexpr (!fresh) Gt[g] = *reinterpret_cast<const f32x4*>(Gb + ycl * lde + u * 16 + r4y);
                 }
             }
@@ -2243,20 +1950,20 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         if constexpr (fresh) {
             // y'' of column ycl, ranks r4..r4+3 and 16+r4..19+r4, summed over the stage-1 splits in order
             f32x4 y0, y1;
-            if constexpr (kBFix) {
-                f32x4 yp[S::NSPLIT], yq[S::NSPLIT], gv[kT][2];
+            if constexpr (PL::kBFix) {
+                f32x4 yp[S::NSPLIT], yq[S::NSPLIT], gv[PL::kTB][2];
 #pragma unroll
                 for (int sp = 0; sp < S::NSPLIT; ++sp) {
                     yp[sp] = *reinterpret_cast<const f32x4*>(Ypart + (sp * 16 + ycl) * ldy + r4y);
                     yq[sp] = *reinterpret_cast<const f32x4*>(Ypart + (sp * 16 + ycl) * ldy + 16 + r4y);
                 }
 #pragma unroll
-                for (int g = 0; g < kT; ++g) {
-                    const int u = pz + g * (MAXT / 64);
+                for (int g = 0; g < PL::kTB; ++g) {
+                    const int u = pz + g * PL::kDW;
                     gv[g][0] = gv[g][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (u < S::NK / 16) {
-                        gv[g][0] = kVRegB ? bvn[g][0] : vn_frag(u * KQ2);
-                        gv[g][1] = kVRegB ? bvn[g][1] : vn_frag(u * KQ2 + 1);
+                    if (u < PL::kMTG) {
+                        gv[g][0] = PL::kVRegB ? bvn[g][0] : vn_frag(u * KQ2);
+                        gv[g][1] = PL::kVRegB ? bvn[g][1] : vn_frag(u * KQ2 + 1);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -2269,9 +1976,9 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                 }
                 // G = V_R·y'' at rank 24 (kR24, the order of stage2f), issued before the norm's VALU work
 #pragma unroll
-                for (int g = 0; g < kT; ++g) {
+                for (int g = 0; g < PL::kTB; ++g) {
                     Gt[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (pz + g * (MAXT / 64) < S::NK / 16) {
+                    if (pz + g * PL::kDW < PL::kMTG) {
 #pragma unroll
                         for (int m = 0; m < 4; ++m) Gt[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(gv[g][0][m], y0[m], Gt[g], 0, 0, 0);
 #pragma unroll
@@ -2300,7 +2007,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             const auto p32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(s2), __float_as_uint(s2), false, false);
             const int cs = __float_as_int(__uint_as_float(p32[0]) + __uint_as_float(p32[1]));
             float g2;
-            if constexpr (D <= 3) {
+            if constexpr (PL::kNormShift) {
                 // the slot's D column sums by in-row shifts (the slot's columns sit in this lane's row; a
                 // helper's own columns hold t*'s sums, from the same y'' columns): same adds in the same order
                 // as the gather below, without its LDS round trips
@@ -2327,7 +2034,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             }
             gn = __builtin_amdgcn_sqrtf(g2);  // v_sqrt_f32 (≤ 1 ulp): every user reads this value (TS)
             if (pz == 0 && lane < kCols && ycl == cl && cl % D == 0) TS[(cl / D) * kTsW + 1] = gn;  // for the trajectories and the later rounds
-            if constexpr (!kBFix) {
+            if constexpr (!PL::kBFix) {
                 const f32x4 g0 = vn_frag(pz * KQ2), g1 = vn_frag(pz * KQ2 + 1);
                 Gt[0] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -2376,11 +2083,11 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], E[2], acc0, 0, 0, 0);
             acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], E[3], acc1, 0, 0, 0);
         };
-        if constexpr (kBFix) {
+        if constexpr (PL::kBFix) {
 #pragma unroll
-            for (int g = 0; g < kT; ++g) {
-                const int u = pz + g * (MAXT / 64);
-                if (u < S::NK / 16) tile(u, Gt[g], fresh, Ap[g], Vp[g]);
+            for (int g = 0; g < PL::kTB; ++g) {
+                const int u = pz + g * PL::kDW;
+                if (u < PL::kMTG) tile(u, Gt[g], fresh, Ap[g], Vp[g]);
             }
         } else {
             for (int u = pz; u < MTG; u += nwaves) {
@@ -2413,19 +2120,19 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     auto bls_f = [&]() {
         const float* zq = Zq + (r4 >> 2) * 64 + cl * 4;
         f32x4 by0, bz;
-        if constexpr (kBFix) {  // every partial read before the first sum (one LDS round trip)
-            f32x4 yp[S::NSPLIT], zz[kNZc];
+        if constexpr (PL::kBFix) {  // every partial read before the first sum (one LDS round trip)
+            f32x4 yp[S::NSPLIT], zz[PL::kNZc];
 #pragma unroll
             for (int sp = 0; sp < S::NSPLIT; ++sp) yp[sp] = *reinterpret_cast<const f32x4*>(Ypart + (sp * 16 + ycl) * ldy + r4y);
 #pragma unroll
-            for (int w = 0; w < kNZc; ++w) zz[w] = *reinterpret_cast<const f32x4*>(zq + w * 256);
+            for (int w = 0; w < PL::kNZc; ++w) zz[w] = *reinterpret_cast<const f32x4*>(zq + w * 256);
             __builtin_amdgcn_sched_barrier(0);
             by0 = yp[0];
 #pragma unroll
             for (int sp = 1; sp < S::NSPLIT; ++sp) by0 += yp[sp];
             bz = zz[0];
 #pragma unroll
-            for (int w = 1; w < kNZc; ++w) bz += zz[w];
+            for (int w = 1; w < PL::kNZc; ++w) bz += zz[w];
         } else {
             by0 = *reinterpret_cast<const f32x4*>(Ypart + ycl * ldy + r4y);
             for (int sp = 1; sp < nsplit; ++sp) by0 += *reinterpret_cast<const f32x4*>(Ypart + (sp * 16 + ycl) * ldy + r4y);
@@ -2433,9 +2140,9 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             for (int w = 1; w < nzp; ++w) bz += *reinterpret_cast<const f32x4*>(zq + w * 256);
         }
         const f32x4 bt = by0 + bz;
-        f32x4 acc[S2T];
+        f32x4 acc[PL::S2T];
 #pragma unroll
-        for (int j = 0; j < S2T; ++j) {
+        for (int j = 0; j < PL::S2T; ++j) {
             acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (wave + j * nwaves < MT2) {
 #pragma unroll
@@ -2443,7 +2150,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             }
         }
 #pragma unroll
-        for (int j = 0; j < S2T; ++j)
+        for (int j = 0; j < PL::S2T; ++j)
             if (wave + j * nwaves < MT2) *reinterpret_cast<f32x4*>(dP + cl * ldx + (wave + j * nwaves) * 16 + r4x) = acc[j];
     };
     // ---- the dense operator (DENSE: DenseShape, F = L = [K; dK], V_R = I — G is y'' and z is e').
@@ -2453,17 +2160,12 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     // waves, the B operand one quad of y'' + e' per k-quad from LDS.  Every operator fragment (Fᵀ, F:
     // 512 KB each at N = 256) is streamed from L2 kDPF k-quads ahead of its MFMAs; a sched_barrier per
     // k-quad keeps the compiler from hoisting the whole stream (its registers) up front.
-    constexpr int kDW = MAXT / 64;
-    constexpr int kD1 = DENSE ? (S::RP / 16 + kDW - 1) / kDW : 1;  // stage-1 row tiles per wave
-    constexpr int kD2 = DENSE ? (S::MP / 16 + kDW - 1) / kDW : 1;  // stage-2 row tiles per wave
-    constexpr int kDQ = DENSE ? S::NK / 16 : 1;                    // k-quads per half
-    constexpr int kDPF = 2;  // prefetch depth (k-quads; 3 and 4 measured the same: the stages are MFMA-bound)
-    float aepd[kD1];  // F_bot rows 0 / N−1 of the wave's stage-1 row tiles (the endpoint MFMA's A)
+    float aepd[PL::kD1];  // F_bot rows 0 / N−1 of the wave's stage-1 row tiles (the endpoint MFMA's A)
 #pragma unroll
-    for (int j = 0; j < kD1; ++j) {
-        const int tl = wave + j * kDW;
+    for (int j = 0; j < PL::kD1; ++j) {
+        const int tl = wave + j * PL::kDW;
         aepd[j] = 0.f;
-        if (DENSE && tl < RP / 16 && (lane >> 4) < 2) aepd[j] = P.Fbot[(size_t)((lane >> 4) ? N - 1 : 0) * RP + tl * 16 + (lane & 15)];
+        if (PL::DENSE && tl < RP / 16 && (lane >> 4) < 2) aepd[j] = P.Fbot[(size_t)((lane >> 4) ? N - 1 : 0) * RP + tl * 16 + (lane & 15)];
     }
     auto dense_stage1 = [&](bool full) {
         const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
@@ -2474,41 +2176,41 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         auto g1ld = [&](int tl, int kq) { return ld_frag(r1, vo, ((tl * KQ1c + kq) * 64) * 16); };
         const float* xl = X + cl * ldx + r4x;
         const float bep = smem[epoff];
-        f32x4 acc[kD1];
+        f32x4 acc[PL::kD1];
 #pragma unroll
-        for (int j = 0; j < kD1; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(aepd[j], bep, z4, 0, 0, 0);
+        for (int j = 0; j < PL::kD1; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(aepd[j], bep, z4, 0, 0, 0);
         auto half = [&](int kb) {  // k-quads kb … kb + kDQ − 1 of Fᵀ's MP columns
-            f32x4 a[kDPF][kD1], b[kDPF];
+            f32x4 a[PL::kDPF][PL::kD1], b[PL::kDPF];
 #pragma unroll
-            for (int p = 0; p < kDPF; ++p) {
+            for (int p = 0; p < PL::kDPF; ++p) {
 #pragma unroll
-                for (int j = 0; j < kD1; ++j) a[p][j] = g1ld(wave + j * kDW, kb + p);
+                for (int j = 0; j < PL::kD1; ++j) a[p][j] = g1ld(wave + j * PL::kDW, kb + p);
                 b[p] = *reinterpret_cast<const f32x4*>(xl + (kb + p) * 16);
             }
 #pragma unroll
-            for (int kq = 0; kq < kDQ; ++kq) {
-                const int sl = kq % kDPF;
-                f32x4 ac[kD1];
+            for (int kq = 0; kq < PL::kDQ; ++kq) {
+                const int sl = kq % PL::kDPF;
+                f32x4 ac[PL::kD1];
 #pragma unroll
-                for (int j = 0; j < kD1; ++j) ac[j] = a[sl][j];
+                for (int j = 0; j < PL::kD1; ++j) ac[j] = a[sl][j];
                 const f32x4 bc = b[sl];
-                if (kq + kDPF < kDQ) {
+                if (kq + PL::kDPF < PL::kDQ) {
 #pragma unroll
-                    for (int j = 0; j < kD1; ++j) a[sl][j] = g1ld(wave + j * kDW, kb + kq + kDPF);
-                    b[sl] = *reinterpret_cast<const f32x4*>(xl + (kb + kq + kDPF) * 16);
+                    for (int j = 0; j < PL::kD1; ++j) a[sl][j] = g1ld(wave + j * PL::kDW, kb + kq + PL::kDPF);
+                    b[sl] = *reinterpret_cast<const f32x4*>(xl + (kb + kq + PL::kDPF) * 16);
                 }
 #pragma unroll
                 for (int m = 0; m < 4; ++m)
 #pragma unroll
-                    for (int j = 0; j < kD1; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[j][m], bc[m], acc[j], 0, 0, 0);
+                    for (int j = 0; j < PL::kD1; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[j][m], bc[m], acc[j], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
         };
         half(0);
-        if (full) half(kDQ);
+        if (full) half(PL::kDQ);
 #pragma unroll
-        for (int j = 0; j < kD1; ++j)
-            *reinterpret_cast<f32x4*>(Ypart + cl * ldy + (wave + j * kDW) * 16 + r4x) = acc[j];
+        for (int j = 0; j < PL::kD1; ++j)
+            *reinterpret_cast<f32x4*>(Ypart + cl * ldy + (wave + j * PL::kDW) * 16 + r4x) = acc[j];
     };
     auto dense_stage2 = [&]() {
         constexpr int KQ2c = S::RP / 16;
@@ -2518,38 +2220,38 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         auto g2ld = [&](int tl, int kq) { return ld_frag(r2, vo, ((tl * KQ2c + kq) * 64) * 16); };
         const float* yl = Ypart + cl * ldy + r4x;
         const float* el = Eb + cl * lde + r4x;
-        f32x4 acc[kD2], a[kDPF][kD2], by[kDPF], be[kDPF];
+        f32x4 acc[PL::kD2], a[PL::kDPF][PL::kD2], by[PL::kDPF], be[PL::kDPF];
 #pragma unroll
-        for (int j = 0; j < kD2; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < PL::kD2; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int p = 0; p < kDPF; ++p) {
+        for (int p = 0; p < PL::kDPF; ++p) {
 #pragma unroll
-            for (int j = 0; j < kD2; ++j) a[p][j] = g2ld(wave + j * kDW, p);
+            for (int j = 0; j < PL::kD2; ++j) a[p][j] = g2ld(wave + j * PL::kDW, p);
             by[p] = *reinterpret_cast<const f32x4*>(yl + p * 16);
             be[p] = *reinterpret_cast<const f32x4*>(el + p * 16);
         }
 #pragma unroll
-        for (int kq = 0; kq < kDQ; ++kq) {
-            const int sl = kq % kDPF;
-            f32x4 ac[kD2];
+        for (int kq = 0; kq < PL::kDQ; ++kq) {
+            const int sl = kq % PL::kDPF;
+            f32x4 ac[PL::kD2];
 #pragma unroll
-            for (int j = 0; j < kD2; ++j) ac[j] = a[sl][j];
+            for (int j = 0; j < PL::kD2; ++j) ac[j] = a[sl][j];
             const f32x4 bt = by[sl] + be[sl];  // y'' + e' (z = V_Rᵀ·e' = e')
-            if (kq + kDPF < kDQ) {
+            if (kq + PL::kDPF < PL::kDQ) {
 #pragma unroll
-                for (int j = 0; j < kD2; ++j) a[sl][j] = g2ld(wave + j * kDW, kq + kDPF);
-                by[sl] = *reinterpret_cast<const f32x4*>(yl + (kq + kDPF) * 16);
-                be[sl] = *reinterpret_cast<const f32x4*>(el + (kq + kDPF) * 16);
+                for (int j = 0; j < PL::kD2; ++j) a[sl][j] = g2ld(wave + j * PL::kDW, kq + PL::kDPF);
+                by[sl] = *reinterpret_cast<const f32x4*>(yl + (kq + PL::kDPF) * 16);
+                be[sl] = *reinterpret_cast<const f32x4*>(el + (kq + PL::kDPF) * 16);
             }
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
-                for (int j = 0; j < kD2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[j][m], bt[m], acc[j], 0, 0, 0);
+                for (int j = 0; j < PL::kD2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac[j][m], bt[m], acc[j], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
-        for (int j = 0; j < kD2; ++j)
-            *reinterpret_cast<f32x4*>(dP + cl * ldx + (wave + j * kDW) * 16 + r4x) = acc[j];
+        for (int j = 0; j < PL::kD2; ++j)
+            *reinterpret_cast<f32x4*>(dP + cl * ldx + (wave + j * PL::kDW) * 16 + r4x) = acc[j];
     };
     // this lane's direction rows Δ = (F·y'')·J for waypoint j (the endpoint velocity rows are in y'')
     auto direction = [&](int j, float (&dt)[D], float (&dv)[D]) {
@@ -2576,7 +2278,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         const int r = wl[j] ? nn[j] : 0;  // (valid trajectories only)
 #pragma unroll
         for (int k = 0; k < D; ++k) {
-            if constexpr (DENSE) G[k] = Ypart[(gt * D + k) * ldy + swz(r, gt * D + k)];  // V_R = I: G = y''
+            if constexpr (PL::DENSE) G[k] = Ypart[(gt * D + k) * ldy + swz(r, gt * D + k)];  // V_R = I: G = y''
             else G[k] = Gb[(gt * D + k) * lde + swz(r, gt * D + k)];
         }
     };
@@ -2584,7 +2286,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     // is a per-lane 64-bit address the 7-DoF dual loop spilled)
     auto ser_row = [&](int j) {
         int r = nn[j] * D;
-        if constexpr (D > 3) asm volatile("" : "+v"(r));
+        if constexpr (PL::kLaunder) asm volatile("" : "+v"(r));
         return r;
     };
     auto snapshot = [&](irm_stats& st) {  // extended-vis frame after a non-breaking inner iteration
@@ -2601,7 +2303,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         }
     };
 
-    // ---- BLS line-search helpers (kHelp, lean_help): when one trajectory t* of the workgroup is left in a
+    // ---- BLS line-search helpers (PL::kHelp): when one trajectory t* of the workgroup is left in a
     // line search, the first done slot evaluates its next trial (lr·β₋, optimizer_BLS.py:143-147) in the
     // same round: a rejected trial changes nothing but lr, so the sequential search's decisions, counters
     // and log are unchanged — only rounds are saved.  The helper reads t*'s α, T, V rows (ss, written by
@@ -2611,9 +2313,8 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     // inputs and α, T, V, which t* adopts at the next round's start.
     float* SS = smem + LX.ss;  // [3·D][MAXT]: α, T, V of the thread's waypoint
     float* HP = smem + LX.hp;  // [slot][kHpW]: lr, ljl, lsg, loss, trial, inner, bfar (per wave of the slot)
-    constexpr int kSlots = (MAXT / 64) / WPTL;
     auto ss_write = [&](int tt, const float (&a)[WPL][D], const float (&qq)[WPL][D], const float (&vv)[WPL][D]) {
-        const int th = tt * NWL + li;
+        const int th = tt * PL::NWL + li;
 #pragma unroll
         for (int k = 0; k < D; ++k) {
             SS[k * MAXT + th] = a[0][k];
@@ -2622,7 +2323,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         }
     };
     auto ss_read = [&](int tt) {
-        const int th = tt * NWL + li;
+        const int th = tt * PL::NWL + li;
 #pragma unroll
         for (int k = 0; k < D; ++k) {
             al[0][k] = SS[k * MAXT + th];
@@ -2637,7 +2338,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         if (n0 == 0 && lane == 0) {
             TS[t * kTsW + 0] = lr;
             TS[t * kTsW + 2] = phase == LP_STEP ? 1.f : 0.f;
-            if constexpr (QUE) TS[t * kTsW + 3] = __int_as_float((int)b);  // the slot's problem, for a helper
+            if constexpr (PL::kQueue) TS[t * kTsW + 3] = __int_as_float((int)b);  // the slot's problem, for a helper
         }
     };
     int n_rounds = 0, n_hm = 0;  // diagnostics (trace_b bit 29): kernel rounds / helper rounds until this trajectory ended
@@ -2645,10 +2346,8 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     // round 0 (optimizer_GD.py:93 / :210: the loss at α0) and the first gradient inputs
     irm_stats st{};
     st.series_len = rec ? 1 : 0;
-    // BLS: the per-trajectory counters in VGPRs (the compiler would keep these wave-uniform values in SGPRs,
-    // and the BLS flow's scalar state spills SGPRs to VGPR lanes — readlane / writelane on the round's path):
-    // C3-BLS −0.9 %, its faithful line −0.4 %, C2 −0.7 %; the GD dual loop 1-1.6 % slower with it, not used
-    if constexpr (BLS && D <= 3) {  // (the 7-DoF BLS variants have no VGPRs to spare)
+    // BLS: the per-trajectory counters in VGPRs
+    if constexpr (PL::kStatVgpr) {
         asm volatile("" : "+v"(st.inner_iterations), "+v"(st.outer_iterations), "+v"(st.grad_evals), "+v"(st.cost_evals),
                      "+v"(st.bls_trials), "+v"(st.series_len), "+v"(n_rounds), "+v"(n_hm));
     }
@@ -2674,13 +2373,13 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         __syncthreads();
         const Fin f = finalize(lsg, t);
         loss = f.nl;
-        if constexpr (!BLS) st.cost_evals = 1;
+        if constexpr (!PL::BLS) st.cost_evals = 1;
         bool to_end = P.max_inner <= 0;
         // BLS with max_outer_iteration <= 0: the outer while_loop never runs and α0 is returned
         // (optimizer_BLS.py:184-186, 210-213): straight to the constraint check
-        if constexpr (BLS) to_end = to_end || P.max_outer <= 0;
+        if constexpr (PL::BLS) to_end = to_end || P.max_outer <= 0;
         bool bfar = false;
-        if constexpr (GD1) {
+        if constexpr (PL::GD1) {
             if (to_end) done = true;
         } else if (to_end) {
             // (a slot without a problem stays LP_DONE: as LP_RESYNC it would run the constraint round, end it and —
@@ -2696,12 +2395,11 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             bfar = grad_inputs(w, q, v, f.idx, lsg, ljl, t);
             xdense = bfar;
         }
-        if constexpr (BLS) {
+        if constexpr (PL::BLS) {
             if (tvalid) ts_write();
         }
-        if constexpr (kHelp) {
+        if constexpr (PL::kHelp) {
             if (tvalid) {
-                if constexpr (!kSSLazy) ss_write(t, al, q, v);
                 if (n0 == 0 && lane == 0) {
                     HP[t * kHpW + 0] = lr;
                     HP[t * kHpW + 1] = ljl;
@@ -2712,24 +2410,18 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                 }
             }
         }
-        if constexpr (GD1) {
+        if constexpr (PL::GD1) {
             if (lane == 0 && (!done || bfar)) atomicOr(&fw[0], (done ? 0u : 1u << wave) | (bfar ? 1u << 31 : 0u));
         } else {
             if (lane == 0 && tvalid)
                 atomicOr(&fw[0], (1u << wave) | (needs_dir ? 1u << 28 : 0u) | (phase == LP_RESYNC ? 1u << 29 : 0u) |
                                      (phase == LP_STEP ? 1u << 30 : 0u) |
-                                     ((BLS ? xdense && phase == LP_STEP : bfar) ? 1u << 31 : 0u));
+                                     ((PL::BLS ? xdense && phase == LP_STEP : bfar) ? 1u << 31 : 0u));
         }
     }
     __syncthreads();
 
     IRM_STAMP(14);
-    // K / dK rows per software-pipelined batch of the resync's eval_exact: the loads are latency-bound
-    // (one L2 round trip per batch), so D = 3 with one waypoint per lane takes 8 rows per batch — no extra
-    // spills there (C3 faithful 4.57 -> 4.42 ms, C3 BLS faithful 5.68 -> 5.60, C2 0.706 -> 0.689, same
-    // box, same sums in the same order); the D = 7 / two-waypoint variants keep 2 (register peak)
-    constexpr bool kReloadOps = D > 3 && MAXT > 256;
-    constexpr int kResyncU = (D <= 3 && WPL == 1) ? 8 : 2;
     // ---------------------------------------------------------- rounds
     // The second half of the waves (4-7: the younger partner on each SIMD) loses VALU arbitration to
     // the older one in every phase; static priority for that half (MI355X_MICROARCH.md, two waves per
@@ -2748,12 +2440,8 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     // away from the endpoints, and a dense round where b' is zero adds exact zeros).
     // The hand-over is the flag word itself: the loop below reads the word this loop declined.
     int par0 = 0;
-    if constexpr (kTopC3) {
-        constexpr int kW1 = (S::RP / 16) * S::NSPLIT;  // the stage-1 waves; the z unit's are all the others
-        static_assert(kW1 + kZS == MAXT / 64 && kZFix && !kZPre && kGLate && kGFin && kLatF && kAllLive && kLeanKeep<D>,
-                      "the all-live loop is written for C3's kernel");
-        if (ntb == kSlots) {  // workgroup-uniform: every slot holds a problem
-            constexpr unsigned kAllW = (1u << (MAXT / 64)) - 1u;
+    if constexpr (PL::kTopC3) {
+        if (ntb == PL::kSlots) {  // workgroup-uniform: every slot holds a problem
             const unsigned wbit = 1u << wave;
             const LeanW cw = lean_weights(P, ljl);
             const f32x4 zpre[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};  // (kVReg: the z unit's fragments are in vtR)
@@ -2763,7 +2451,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             bool rej = false;  // left through a rejected step (one more gradient and cost evaluation)
             int par = 0;
             for (;; par ^= 1) {
-                f32x4 pre1[KQU1], pre1w[KQU1];
+                f32x4 pre1[PL::KQU1], pre1w[PL::KQU1];
                 float pre1e = 0.f;
                 unsigned fl = 0u;
                 const unsigned flv = fw[par];
@@ -2773,7 +2461,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                 if (has1) {  // wave-uniform
                     stage1_load(pre1, pre1w, pre1e);
                     asm volatile("v_readfirstlane_b32 %0, %1 ; flag word, stage-1 waves (all-live)" : "=s"(fl) : "v"(flv));
-                    if ((fl & kAllW) != kAllW) break;
+                    if ((fl & PL::kAllW) != PL::kAllW) break;
                     IRM_STAMP(0);
                     IRM_COUNT(13, (fl >> 31) != 0u);
                     stage1((fl >> 31) != 0u, pre1, pre1w, pre1e);
@@ -2782,7 +2470,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                     if (wave == 0) fw[par ^ 1] = 0u;
                 } else {
                     asm volatile("v_readfirstlane_b32 %0, %1 ; flag word, z waves (all-live)" : "=s"(fl) : "v"(flv));
-                    if ((fl & kAllW) != kAllW) break;
+                    if ((fl & PL::kAllW) != PL::kAllW) break;
                     stage1z(zpre);
                 }
                 IRM_STAMP(1);
@@ -2882,14 +2570,14 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         }
     }
     for (int par = par0;; par ^= 1) {
-        f32x4 pre1[KQU1], pre1w[KQU1];
-        f32x4 zpre[kZPre ? kKQZ : 1];
+        f32x4 pre1[PL::KQU1], pre1w[PL::KQU1];
+        f32x4 zpre[PL::kZPre ? PL::kKQZ : 1];
         zpre_load(zpre);
         float pre1e = 0.f;  // read only on the endpoint waves (hasep)
         // (the flag word read before the operand batch, so the branch need not wait for the batch: C3 even
         // to 2 % slower, not kept)
         unsigned flw = 0u;
-        if constexpr (kS1Ord) {
+        if constexpr (PL::kS1Ord) {
             // C3's kernel: the flag word first, then the stage-1 waves' operands in the order of their use, all
             // in one LDS queue.  The flag becomes a scalar inside each wave class's own block, so its wait
             // counts that block's later reads (lgkmcnt(9) on the stage-1 waves) instead of draining them,
@@ -2904,25 +2592,25 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                 asm volatile("v_readfirstlane_b32 %0, %1 ; flag word, other waves" : "=s"(flw) : "v"(flv));
             }
         }
-        if constexpr (kPre1 && !kS1Ord) stage1_load(pre1, pre1w, pre1e);
-        const unsigned fl = kS1Ord ? flw : fw[par];
-        if constexpr (GD1) {
+        if constexpr (PL::kPre1 && !PL::kS1Ord) stage1_load(pre1, pre1w, pre1e);
+        const unsigned fl = PL::kS1Ord ? flw : fw[par];
+        if constexpr (PL::GD1) {
             if ((fl & 0x7FFFFFFFu) == 0u) break;  // every trajectory of the block is done
         } else {
             if ((fl & 0xFFFFu) == 0u) break;
         }
         const bool dense = (fl >> 31) != 0u;
-        const bool dirr = GD1 || ((fl >> 28) & 1u);  // some trajectory needs a direction this round
-        const bool rsy = !GD1 && ((fl >> 29) & 1u);  // some trajectory ends an inner loop this round
+        const bool dirr = PL::GD1 || ((fl >> 28) & 1u);  // some trajectory needs a direction this round
+        const bool rsy = !PL::GD1 && ((fl >> 29) & 1u);  // some trajectory ends an inner loop this round
         // (kS1Ord: cleared behind stage 1 — here the store's wait drained wave 0's operand batch)
-        if constexpr (!kS1Ord) {
+        if constexpr (!PL::kS1Ord) {
             if (tid == 0) fw[par ^ 1] = 0u;
         }
-        if constexpr (QUE) {
+        if constexpr (PL::kQueue) {
             // the index this slot's first wave took at the end of the previous round (its record's spare word):
             // a problem to load this round, or past the batch — the slot stays done
             if (qpend) {
-                const int nx = __builtin_amdgcn_readfirstlane(__float_as_int(red[(t * WPTL) * 8 + 6]));
+                const int nx = __builtin_amdgcn_readfirstlane(__float_as_int(red[(t * PL::WPTL) * 8 + 6]));
                 qpend = false;
                 if (nx < P.B) {
                     b = (size_t)nx;
@@ -2934,18 +2622,18 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         int ts = 0, hs = 0;               // t*, the helper slot
         float h_lr0 = 0.f, h_lr = 0.f, h_ljl = 0.f, h_lsg = 0.f, h_loss = 0.f, h_gn = 1.f, h_an = 0.f;
         int h_trial = 0, h_inner = 0;
-        if constexpr (kHelp) {
+        if constexpr (PL::kHelp) {
             n_rounds++;
             if (adopt) {  // t*: the previous round accepted the helper's trial
                 ss_read(t);
-                xdense = HP[t * kHpW + 6 + (wave - t * WPTL)] != 0.f;
+                xdense = HP[t * kHpW + 6 + (wave - t * PL::WPTL)] != 0.f;
                 adopt = false;
             }
-            if (!rec && !P.lean_nohelp && ((fl >> 30) & 1u) && kSlots > 1) {
+            if (!rec && !P.lean_nohelp && ((fl >> 30) & 1u) && PL::kSlots > 1) {
                 unsigned live = 0u;
 #pragma unroll
-                for (int s2 = 0; s2 < kSlots; ++s2)
-                    if ((fl >> (s2 * WPTL)) & ((1u << WPTL) - 1u)) live |= 1u << s2;
+                for (int s2 = 0; s2 < PL::kSlots; ++s2)
+                    if ((fl >> (s2 * PL::WPTL)) & ((1u << PL::WPTL) - 1u)) live |= 1u << s2;
                 if (__builtin_popcount(live) == 1) {
                     hm = true;
                     n_hm++;
@@ -2973,18 +2661,15 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             // rounds end measured C3-BLS faithful +0.8 %, C2 even, and is not done; priority only reorders issue)
             // t* publishes its α, T, V for the helper at the top of each helper round (the helper reads them
             // after this round's G-tile barrier), instead of after every accepted trial of every trajectory
-            if constexpr (kSSLazy) {
-                if (hm && t == ts) ss_write(t, al, q, v);
-            }
+            if (hm && t == ts) ss_write(t, al, q, v);
             if (helper) {  // wave-uniform: t*'s state and scalars (its own trajectory is done and written out)
-                if constexpr (!kSSLazy) ss_read(ts);
                 // t*'s problem: its place in the launch, or (QUE) the index its slot claimed
-                const size_t bs = QUE ? (size_t)__float_as_int(TS[ts * kTsW + 3]) : (size_t)(tb0 + ts);
+                const size_t bs = PL::kQueue ? (size_t)__float_as_int(TS[ts * kTsW + 3]) : (size_t)(tb0 + ts);
 #pragma unroll
                 for (int k = 0; k < D; ++k) tg[0][k] = (nn[0] == N - 1) ? P.goal[bs * D + k] : P.start[bs * D + k];
                 vl[0] = wl[0];
                 obs = obsL + (P.obs_stride ? ts * obs_pitch(P.O) : 0);  // t*'s obstacles (per-problem sets)
-                if constexpr (OREG) {  // (the register copy of the table too)
+                if constexpr (PL::OREG) {  // (the register copy of the table too)
                     if (P.obs_stride && obs_reg) {
 #pragma unroll
                         for (int i = 0; i < 6; ++i) oreg[i] = reinterpret_cast<const f32x4*>(obs)[i];
@@ -3002,29 +2687,29 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             }
         }
         IRM_STAMP(0);
-        if constexpr (!BLS) {
+        if constexpr (!PL::BLS) {
             if (dirr) {  // block-uniform
                 IRM_COUNT(13, dense);
-                if constexpr (DENSE) {
+                if constexpr (PL::DENSE) {
                     dense_stage1(dense);
                 } else {
                     stage1(dense, pre1, pre1w, pre1e);
                     stage1z(zpre);
                     // the next round's flag word: last read at the previous round's top, next set by this
                     // round's decisions (two barriers on either side)
-                    if constexpr (kS1Ord) {
+                    if constexpr (PL::kS1Ord) {
                         if (tid == 0) fw[par ^ 1] = 0u;
                     }
                 }
                 IRM_STAMP(1);
                 __syncthreads();
                 IRM_STAMP(2);
-                if constexpr (DENSE) dense_stage2();
+                if constexpr (PL::DENSE) dense_stage2();
                 else stage2f(std::true_type{}, std::true_type{});
                 IRM_STAMP(3);
                 __syncthreads();
                 IRM_STAMP(4);
-                if constexpr (kGLate) glate_tiles();
+                if constexpr (PL::kGLate) glate_tiles();
             }
         } else if ((fl >> 30) & 1u) {  // block-uniform: some trajectory has a line-search trial this round
             // (a round with a new direction: stage 1 first; the trial stages of bls_gz / bls_f, above)
@@ -3061,14 +2746,14 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             IRM_STAMP(3);
             __syncthreads();
             IRM_STAMP(4);
-            if constexpr (kSSLazy) {
+            if constexpr (PL::kHelp) {
                 if (helper) ss_read(ts);  // (t* wrote them at this round's top)
             }
             bls_f();
             __syncthreads();
         }
         // ------------------------------------------------ BLS: a new direction (the inner-loop head)
-        if constexpr (BLS) {
+        if constexpr (PL::BLS) {
             if (needs_dir) {  // wave-uniform; optimizer_BLS.py:163-166
                 gnorm = TS[t * kTsW + 1];  // ‖G‖ as the trial stages used it (bls_gz)
                 anorm = wp[t * 2 + 1] / gnorm;
@@ -3080,7 +2765,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         }
         // this round's step (BLS: the trial's; a helper's: t*'s next trial, lr·β₋)
         float cj = cfac, stepj = lr, lrj = lr, gnj = gnorm;
-        if constexpr (BLS) {
+        if constexpr (PL::BLS) {
             if (helper) {
                 h_gn = TS[ts * kTsW + 1];  // t*'s ‖G‖ and alpha_norm, the same values as t*'s latch
                 h_an = wp[ts * 2 + 1] / h_gn;
@@ -3092,8 +2777,8 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         }
         // ------------------------------------------------ end of an inner loop: α's exact trajectory
         if (rsy) {  // block-uniform
-            const bool rs = phase == LP_RESYNC || (QUE && phase == LP_LOAD);  // wave-uniform
-            if constexpr (QUE) {
+            const bool rs = phase == LP_RESYNC || (PL::kQueue && phase == LP_LOAD);  // wave-uniform
+            if constexpr (PL::kQueue) {
                 if (phase == LP_LOAD) {
                     // the claimed problem b into this slot: everything the prologue sets per trajectory.  The
                     // slot's registers may have served as a helper (vl, obs, tg, oreg), its LDS rows and words
@@ -3117,7 +2802,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                             al[0][k] = vl[0] ? un * sj + wn * gj : 0.f;
                         }
                     }
-                    if constexpr (BLS) {  // the α rows of the trial stages
+                    if constexpr (PL::BLS) {  // the α rows of the trial stages
                         if (vl[0]) {
 #pragma unroll
                             for (int k = 0; k < D; ++k) Ab[(t * D + k) * lde + swz(nn[0], t * D + k)] = al[0][k];
@@ -3126,14 +2811,14 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                     obs = obsL + (P.obs_stride ? t * obs_pitch(P.O) : 0);
                     if (P.obs_stride) {  // the problem's own obstacle table (stage_obstacles' layout)
                         const int pitch = obs_pitch(P.O);
-                        for (int r = li; r < pitch; r += NWL) {
+                        for (int r = li; r < pitch; r += PL::NWL) {
                             const int o = 2 * (r >> 2) + (r & 1), coord = (r >> 1) & 1;
                             obsL[t * pitch + r] = o < P.O ? P.obstacles[b * P.obs_stride + 2 * o + coord] : 1.0e20f;
                         }
                     }
                     lsg = P.lsg0;
                     ljl = P.ljl0;
-                    lr = BLS ? P.bls_lr0 : P.gd_lr[0];
+                    lr = PL::BLS ? P.bls_lr0 : P.gd_lr[0];
                     cfac = P.gd_c[0];
                     gnorm = 1.f;
                     anorm = 0.f;
@@ -3150,13 +2835,13 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
 #pragma unroll
                         for (int k = 0; k < D; ++k) {
                             X[(t * D + k) * ldx + lnd(nn[j])] = al[j][k];
-                            if constexpr (!BLS) Eb[(t * D + k) * lde + swz(nn[j], t * D + k)] = 0.f;  // absorbed by the exact trajectory
+                            if constexpr (!PL::BLS) Eb[(t * D + k) * lde + swz(nn[j], t * D + k)] = 0.f;  // absorbed by the exact trajectory
                         }
                     }
                 }
             }
             __syncthreads();
-            if constexpr (QUE && OREG) {  // (the register copy of the loaded problem's table)
+            if constexpr (PL::kQueOreg) {  // (the register copy of the loaded problem's table)
                 if (phase == LP_LOAD && P.obs_stride && obs_reg) {
 #pragma unroll
                     for (int i = 0; i < 6; ++i) oreg[i] = reinterpret_cast<const f32x4*>(obs)[i];
@@ -3166,7 +2851,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
 #pragma unroll
                 for (int j = 0; j < WPL; ++j) {
                     if (vl[j]) {
-                        if constexpr (D <= 3) eval_exact<D, kResyncU, true>(P, X + (t * D) * ldx, nn[j], q[j], v[j], nullptr, nullptr, 1, ldx, Jl);
+                        if constexpr (PL::kResyncBatch) eval_exact<D, PL::kResyncU, true>(P, X + (t * D) * ldx, nn[j], q[j], v[j], nullptr, nullptr, 1, ldx, Jl);
                         else eval_exact_loop<D, 4>(P, X + (t * D) * ldx, ldx, nn[j], N, Jl, q[j], v[j]);
                         // the last extended-vis frame shows the exact trajectory of the returned α (frame 0
                         // stays the initial trajectory, as in k_optimize)
@@ -3180,7 +2865,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             }
             // the operator fragments again (from L2): so they are not live across the resync's exact
             // evaluation, whose register peak spilled them (the 7-DoF dual-loop / BLS kernels)
-            if constexpr (kReloadOps) {
+            if constexpr (PL::kReloadOps) {
                 asm volatile("" ::: "memory");
                 load_ops();
             }
@@ -3189,16 +2874,12 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
         // ------------------------------------------------ update + evaluate
         float q2[WPL][D], v2[WPL][D];
         WP<D> w[WPL];
-        // the GD single loop's G rows of the α update read with the direction (stage 2 wrote both), so their
-        // LDS round trip is off the decision's path: C3 −1.3 %; the dual loop, C5 and C7 measured 0.8-1 %
-        // slower with it (bit-identical either way)
-        constexpr bool kGPre = GD1 && D <= 3 && !kGLate;
-        float Gp[kGPre ? WPL : 1][D];
-        // BLS: this slot's trial iterate α_j read with the direction (bls_gz wrote it), off the accept's path
-        constexpr bool kAjPre = BLS;
-        float Ajp[kAjPre ? WPL : 1][D];
-        const bool stepping = GD1 ? !done : (phase == LP_STEP || helper);  // wave-uniform
-        const bool ev = GD1 ? !done : (phase != LP_DONE || helper);
+        // (PL::kGPre) the GD single loop's G rows of the α update read with the direction (stage 2 wrote both)
+        float Gp[PL::kGPre ? WPL : 1][D];
+        // (PL::kAjPre) BLS: this slot's trial iterate α_j read with the direction (bls_gz wrote it)
+        float Ajp[PL::kAjPre ? WPL : 1][D];
+        const bool stepping = PL::GD1 ? !done : (phase == LP_STEP || helper);  // wave-uniform
+        const bool ev = PL::GD1 ? !done : (phase != LP_DONE || helper);
         if (ev) {
 #pragma unroll
             for (int j = 0; j < WPL; ++j) {
@@ -3206,8 +2887,8 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                     float dt[D], dv[D];
                     {
                         direction(j, dt, dv);
-                        if constexpr (kGPre) grad_alpha(j, Gp[j], t);
-                        if constexpr (kAjPre) {
+                        if constexpr (PL::kGPre) grad_alpha(j, Gp[j], t);
+                        if constexpr (PL::kAjPre) {
 #pragma unroll
                             for (int k = 0; k < D; ++k) Ajp[j][k] = Ajb[(t * D + k) * lde + swz(wl[j] ? lnd(nn[j]) : 0, t * D + k)];
                         }
@@ -3218,7 +2899,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                             v2[j][k] = fmaf(cj, v[j][k], tv);
                             // the products stay live past the FMAs: three-address FMAs, whose results
                             // can take the waypoint state's own registers (no copies at the round's end)
-                            if constexpr (GD1) asm volatile("" ::"v"(tq), "v"(tv), "v"(q2[j][k]), "v"(v2[j][k]));
+                            if constexpr (PL::GD1) asm volatile("" ::"v"(tq), "v"(tv), "v"(q2[j][k]), "v"(v2[j][k]));
                         }
                     }
                 } else {
@@ -3230,7 +2911,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                 }
             }
             IRM_STAMP(5);
-            if constexpr (GD1) {
+            if constexpr (PL::GD1) {
                 // the GD single loop's waypoint state moves to the trial point unconditionally: a
                 // rejected step ends the trajectory, whose q / v are not read again (the epilogue
                 // evaluates α exactly) — no copies on the accept path
@@ -3244,11 +2925,11 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             }
             // an inner loop's end is evaluated with the next outer iteration's λ (its loss and gradient
             // start that iteration; the constraint terms do not depend on λ)
-            const bool rs = !GD1 && phase == LP_RESYNC;
+            const bool rs = !PL::GD1 && phase == LP_RESYNC;
             evaluate(q2, v2, rs, helper ? h_ljl : rs ? ljl * P.lci : ljl, w);
         }
         IRM_STAMP(7);
-        if constexpr (WPTL > 1) {
+        if constexpr (PL::WPTL > 1) {
             __syncthreads();  // the trajectory's wave partials come from several waves
         } else if (hm) {      // block-uniform: t* reads the helper's records
             __syncthreads();
@@ -3257,7 +2938,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             asm volatile("" ::: "memory");
         }
         IRM_STAMP(8);
-        if constexpr (kHelp) {
+        if constexpr (PL::kHelp) {
             if (helper) {  // replay t*'s decision up to this trial: is it the accepted one?
                 const Fin f0 = finalize(h_lsg, ts);
                 if (f0.nl > h_loss - P.bls_a * h_lr0 * h_an && h_trial + 1 < P.max_bls) {
@@ -3268,14 +2949,14 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                         float ajh[WPL][D];
 #pragma unroll
                         for (int k = 0; k < D; ++k) {
-                            ajh[0][k] = kAjPre ? Ajp[0][k] : Ajb[(t * D + k) * lde + swz(nn[0], t * D + k)];
+                            ajh[0][k] = PL::kAjPre ? Ajp[0][k] : Ajb[(t * D + k) * lde + swz(nn[0], t * D + k)];
                             if (wl[0]) Ab[(ts * D + k) * lde + swz(nn[0], ts * D + k)] = ajh[0][k];
                         }
                         ss_write(ts, ajh, q2, v2);
                         if (!(h_loss - f1.nl < P.llr) && h_inner + 1 < P.max_inner) {
                             const bool bf = grad_inputs(w, q2, v2, f1.idx, h_lsg, h_ljl, ts);  // t*'s columns
                             if (lane == 0) {
-                                HP[ts * kHpW + 6 + (wave - t * WPTL)] = bf ? 1.f : 0.f;
+                                HP[ts * kHpW + 6 + (wave - t * PL::WPTL)] = bf ? 1.f : 0.f;
                                 if (bf) atomicOr(&fw[par ^ 1], 1u << 31);
                             }
                         }
@@ -3284,22 +2965,21 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             }
         }
         if (ev && !helper) {
-            const bool rs = !GD1 && phase == LP_RESYNC;
+            const bool rs = !PL::GD1 && phase == LP_RESYNC;
             const float lsg_e = rs ? lsg * P.lci : lsg;
             // (kGFin) the lane's G words of the α update read in one batch with finalize's records (glate_tiles
             // wrote Gb before the evaluation's barrier; finalize's reads stay behind its scheduling barrier):
             // the accepted step waits on no LDS read of its own; a rejected step leaves them unused
-            float Gf[kGFin ? WPL : 1][D];
-            if constexpr (kGFin) {
-                static_assert(kGLate && !kGPre, "G is read after the evaluation's barrier");
+            float Gf[PL::kGFin ? WPL : 1][D];
+            if constexpr (PL::kGFin) {
 #pragma unroll
                 for (int j = 0; j < WPL; ++j) grad_alpha(j, Gf[j], t);
             }
             const Fin f = finalize(lsg_e, t);
             IRM_STAMP(9);
             bool bfar = false, to_end = false, accept = false, snap = false, more = false;
-            if constexpr (!BLS) needs_dir = false;  // GD: every step consumes its direction
-            if constexpr (GD1) {
+            if constexpr (!PL::BLS) needs_dir = false;  // GD: every step consumes its direction
+            if constexpr (PL::GD1) {
                 st.grad_evals++;
                 st.cost_evals++;
                 if (loss - f.nl < P.llr) {
@@ -3312,12 +2992,12 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                     if (inner >= P.max_inner) done = true;
                     else more = true;
                 }
-            } else if (QUE && phase == LP_LOAD) {
+            } else if (PL::kQueue && phase == LP_LOAD) {
                 // round 0 of the loaded problem (optimizer_GD.py:93 / :210: the loss at α0), as after the prologue
                 loss = f.nl;
-                if constexpr (!BLS) st.cost_evals = 1;
+                if constexpr (!PL::BLS) st.cost_evals = 1;
                 bool te = P.max_inner <= 0;
-                if constexpr (BLS) te = te || P.max_outer <= 0;  // α0 is returned (optimizer_BLS.py:184-186)
+                if constexpr (PL::BLS) te = te || P.max_outer <= 0;  // α0 is returned (optimizer_BLS.py:184-186)
                 if (te) {
                     to_end = true;
                 } else {
@@ -3329,7 +3009,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                 // trajectory; optimizer_GD.py:214-224 / optimizer_BLS.py:196-208
                 const bool ok = sqrtf(f.a0) < P.eps_p && sqrtf(f.a1) < P.eps_p && sqrtf(f.b0) < P.eps_v &&
                                 sqrtf(f.b1) < P.eps_v && f.tx <= P.pmax && f.tn >= P.pmin && f.va <= P.vmax;
-                if (!BLS || P.max_outer > 0) st.outer_iterations++;
+                if (!PL::BLS || P.max_outer > 0) st.outer_iterations++;
                 st.constraints_ok = ok ? 1 : 0;
                 outer++;
                 if (ok || outer >= P.max_outer) {
@@ -3339,7 +3019,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                     ljl = ljl * P.lci;
                     loss = f.nl;
                     inner = 0;
-                    if constexpr (BLS) {
+                    if constexpr (PL::BLS) {
                         lr = P.bls_lr0;
                     } else {
                         lr = P.gd_lr[outer];
@@ -3353,7 +3033,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                         more = true;
                     }
                 }
-            } else if constexpr (!BLS) {  // GD dual loop inner step (optimizer_GD.py:180-195)
+            } else if constexpr (!PL::BLS) {  // GD dual loop inner step (optimizer_GD.py:180-195)
                 st.grad_evals++;
                 st.cost_evals++;
                 if (loss - f.nl < P.llr) {
@@ -3372,7 +3052,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                 float improve = 0.f;
                 // this round's trials in the sequential order: t*'s own, then (helper round) the helper's
 #pragma unroll
-                for (int kk = 0; kk < (kHelp ? 2 : 1); ++kk) {
+                for (int kk = 0; kk < (PL::kHelp ? 2 : 1); ++kk) {
                     if (kk == 1 && (!hm || accept || inner_end)) break;  // (the helper's trial was not reached)
                     const Fin fk = kk == 0 ? f : finalize(lsg_e, hs);
                     st.cost_evals++;
@@ -3426,7 +3106,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                     }
                 }
             }
-            if (accept && BLS) {
+            if (accept && PL::BLS) {
                 // the trial's iterate α_j (formed by the trial stages, bls_gz) and its trajectory
                 // (optimizer_BLS.py:149); α_j into the α rows for the next trial stages
 #pragma unroll
@@ -3435,7 +3115,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                     for (int k = 0; k < D; ++k) {
                         const int o = (t * D + k) * lde + swz(wl[j] ? lnd(nn[j]) : 0, t * D + k);
                         if (wl[j]) {
-                            al[j][k] = kAjPre ? Ajp[j][k] : Ajb[o];
+                            al[j][k] = PL::kAjPre ? Ajp[j][k] : Ajb[o];
                             Ab[o] = al[j][k];
                         }
                         q[j][k] = q2[j][k];
@@ -3444,14 +3124,14 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
             } else if (accept) {
                 // α' = fl(fl(c·α) − fl(lr·G)) (optimizer_GD.py:81) and its residual for the next direction
                 // (−e/lr folded into stage 2's y'')
-                const float ne = GD1 ? nilr : -1.f / fmaxf(stepj, kMinRefStep);
+                const float ne = PL::GD1 ? nilr : -1.f / fmaxf(stepj, kMinRefStep);
 #pragma unroll
                 for (int j = 0; j < WPL; ++j) {
                     float G[D];
-                    if constexpr (kGPre) {
+                    if constexpr (PL::kGPre) {
 #pragma unroll
                         for (int k = 0; k < D; ++k) G[k] = Gp[j][k];
-                    } else if constexpr (kGFin) {
+                    } else if constexpr (PL::kGFin) {
 #pragma unroll
                         for (int k = 0; k < D; ++k) G[k] = Gf[j][k];
                     } else {
@@ -3462,7 +3142,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
 #pragma unroll
                     for (int k = 0; k < D; ++k) {
                         al[j][k] = alpha_step_gd2(al[j][k], cj, stepj, G[k], ne, eo[k]);
-                        if constexpr (!GD1) {
+                        if constexpr (!PL::GD1) {
                             q[j][k] = q2[j][k];
                             v[j][k] = v2[j][k];
                         }
@@ -3478,23 +3158,22 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                 st.final_loss = loss;
                 phase = LP_RESYNC;
             }
-            if constexpr (GD1) {
+            if constexpr (PL::GD1) {
                 if (more) bfar = grad_inputs(w, q2, v2, f.idx, lsg, ljl, t);
                 if (lane == 0 && (!done || bfar))
                     atomicOr(&fw[par ^ 1], (done ? 0u : 1u << wave) | (bfar ? 1u << 31 : 0u));
             } else {
                 if (more) {
-                    if (!(kHelp && adopt)) {  // (adopted: the helper wrote the gradient inputs)
+                    if (!(PL::kHelp && adopt)) {  // (adopted: the helper wrote the gradient inputs)
                         bfar = grad_inputs(w, q2, v2, f.idx, lsg, ljl, t);
                         xdense = bfar;
                     }
                     needs_dir = true;
                 }
-                if constexpr (BLS) ts_write();  // the next round's trial stages read lr and the phase
-                if constexpr (kHelp) {
-                    // publish this trajectory's state for a helper: α, T, V when they changed (an accepted
-                    // trial of its own, a new outer iteration's exact trajectory), the scalars every round
-                    if (!kSSLazy && phase == LP_STEP && (accept || rs)) ss_write(t, al, q, v);
+                if constexpr (PL::BLS) ts_write();  // the next round's trial stages read lr and the phase
+                if constexpr (PL::kHelp) {
+                    // publish this trajectory's scalars for a helper, every round (α, T, V: at the top of a
+                    // helper round)
                     if (phase != LP_DONE && n0 == 0 && lane == 0) {
                         HP[t * kHpW + 0] = lr;
                         HP[t * kHpW + 1] = ljl;
@@ -3509,16 +3188,16 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                         write_out();
                     }
                 }
-                if constexpr (QUE) {
+                if constexpr (PL::kQueue) {
                     if (phase == LP_DONE) {  // (only valid slots get here)
-                        if constexpr (!kHelp) write_out();
+                        if constexpr (!PL::kHelp) write_out();
                         // the next problem: one lane of the slot's first wave takes an index; the slot's waves
                         // read it after the round-end barrier.  A problem to load keeps the slot's wave bits
                         // set and asks for a resync round (its carrier)
                         if (n0 == 0 && lane == 0) {
                             const int nx = atomicAdd(P.queue, 1);
                             red[wave * 8 + 6] = __int_as_float(nx);
-                            if (nx < P.B) atomicOr(&fw[par ^ 1], (((1u << WPTL) - 1u) << wave) | 1u << 29);
+                            if (nx < P.B) atomicOr(&fw[par ^ 1], (((1u << PL::WPTL) - 1u) << wave) | 1u << 29);
                         }
                         qpend = true;
                     }
@@ -3529,7 +3208,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
                                                // BLS: every trajectory in a line search keeps the velocity
                                                // half on while its inputs have one (its Ypart / Gb columns
                                                // are recomputed by other trajectories' direction rounds)
-                                               ((BLS ? xdense && phase == LP_STEP : bfar) ? 1u << 31 : 0u));
+                                               ((PL::BLS ? xdense && phase == LP_STEP : bfar) ? 1u << 31 : 0u));
             }
         }
         IRM_STAMP(11);
@@ -3538,7 +3217,7 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     }
 
     // ---------------------------------------------------------- epilogue
-    if constexpr (GD1) {
+    if constexpr (PL::GD1) {
         // T = eval_exact(α) (correctly rounded K·α·J), constraintsFulfilled(α) (trajectory.py:129-137,
         // robot.py:90-113) on it.  Every wave has left the loop after its last barrier: X is free.
         st.final_loss = loss;
@@ -3568,393 +3247,12 @@ __global__ __launch_bounds__(MAXT, (MAXT <= 256 && WPL == 1) ? 2 : 1) void k_lea
     }
     // (LF_GD2 / LF_BLS: every trajectory ended through LP_RESYNC — q, v are α's exact trajectory;
     // kHelp: written when the trajectory finished)
-    if (!kHelp && !QUE && tvalid) write_out();
+    if (!PL::kHelp && !PL::kQueue && tvalid) write_out();
     if (tid == 0) prof.flush(P.prof);
 }
 
-// --------------------------------------------------- α-space eval kernels
-// mode 0: evaluate (K or dK)·α·J; 1: cost; 2: cost + grad; 3: constraints.
-// trajectory.py:63-65, 271-297, 129-180; same lane mapping as k_optimize.
-template <int D, int MAXT>
-__global__ __launch_bounds__(MAXT) void k_forward(KParams P, int mode) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const Plan L = plan_lds(P, false, false, false, P.moving != 0, P.via != 0);
-    const int tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int N = P.N, NW = P.NW, TB = P.TB, MP = P.MP;
-    const int WPT = NW >> 6;
-    const int t = wave / WPT;
-    const int n = tid - t * NW;
-    const int tb0 = blockIdx.x * TB;
-    const int ntb = min(TB, P.B - tb0);
-    if (ntb <= 0) return;
-    const bool tvalid = t < ntb;
-    const bool valid = tvalid && n < N;
-    const size_t b = (size_t)(tb0 + (tvalid ? t : 0));
-    float* XG = smem + L.X;
-    float* red = smem + L.red;
-    float* sg = smem + L.sg;
-    float* obsL = smem + L.obs;
-    float* viaw = smem + L.via;  // (a via launch: L.via is a region of its own)
-
-    stage_obstacles<true>(P, tb0, ntb, obsL);
-    stage_alpha<D>(P, tb0, ntb, XG, MP);
-    __syncthreads();
-    float q[D], v[D], s[D], g[D];
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        q[k] = v[k] = 0.f;
-        s[k] = tvalid ? P.start[b * D + k] : 0.f;
-        g[k] = tvalid ? P.goal[b * D + k] : 0.f;
-    }
-    if (valid) eval_exact<D>(P, XG + t * D, n, q, v);
-    __syncthreads();
-    if (mode == 0) {
-        if (valid) {
-#pragma unroll
-            for (int k = 0; k < D; ++k) P.out0[(b * N + n) * D + k] = P.which ? v[k] : q[k];
-        }
-        return;
-    }
-    WP<D> w;
-    const bool task_row = P.task && valid && n == N - 1;
-    float task_r2 = 0.f;
-    // via-points: the lane of row m_v (rows lie in 1 … N−2, so never a start / goal row)
-    const int via = (P.via && valid) ? via_code(P, n) : -1;
-    if (tvalid) {
-        // (obstacles: shared only here, obs_stride 0 — the velocity table follows the one position table)
-        EE<D> ee;
-        if (valid) eval_waypoint_rt<D, true>(P, q, v, obsL, w, obsL + obs_vel_offset(P), P.moving ? P.tsup[n] : 0.f, &ee);
-        // end-effector goal: ge = J_eeᵀ·(f − p) replaces this lane's copy of the joint goal
-        if (task_row) task_end_row<D>(ee, P.goal_xy[b * 2], P.goal_xy[b * 2 + 1], g, task_r2);
-        // via row: ge_v replaces this lane's copy of the joint goal (an interior row never reads it) and r_v²
-        // goes to the trajectory's via words
-        if (via >= 0) {
-            float r2 = 0.f;
-            via_row_terms<D, false>(P, b, via, q, ee, g, r2);
-            viaw[t * IRM_MAX_VIA + (via & 3)] = r2;
-        }
-        eval_partials<D>(P, valid, w, n, wave, q, v, s, g, red, sg, t, task_row, task_r2);
-    }
-    __syncthreads();
-    EvalOut E{};
-    const int nvia = P.via ? P.n_via : 0;
-    if (tvalid) E = eval_finalize(P, red, sg, t, t * WPT, WPT, P.lam_sg, P.lam_jl, viaw, nvia);
-    if (tvalid && n == 0) {
-        if (mode == 1 || mode == 2) {
-            if (P.out0) P.out0[b] = E.loss;
-        } else if (mode == 3) {
-            const bool f0 = E.ds < P.eps_p && E.dg < P.eps_p;
-            const bool f1 = E.vs < P.eps_v && E.vg < P.eps_v;
-            const bool f2 = E.tmax <= P.pmax && E.tmin >= P.pmin;
-            const bool f3 = E.vabs <= P.vmax;
-            bool fv = true;  // every via distance below eps_position (the 11-float report stays as it is)
-            for (int i = 0; i < nvia; ++i) {
-                const float dv = sqrtf(viaw[t * IRM_MAX_VIA + i]);
-                fv = fv && dv < P.eps_p;
-                if (P.out1) P.out1[b * nvia + i] = dv;
-            }
-            if (P.out_ok) P.out_ok[b] = (f0 && f1 && f2 && f3 && fv) ? 1 : 0;
-            if (P.out0) {
-                float* r = P.out0 + b * 11;
-                r[0] = E.ds; r[1] = E.dg; r[2] = E.vs; r[3] = E.vg;
-                r[4] = E.tmax; r[5] = E.tmin; r[6] = E.vabs;
-                r[7] = f0; r[8] = f1; r[9] = f2; r[10] = f3;
-            }
-        }
-    }
-    if (mode != 2) return;
-    if (valid) {
-        float a[D], bb[D];
-        grad_waypoint<D>(P, w, q, v, n, E.idx, P.lam_sg, P.lam_jl, s, g, a, bb, task_row, via >= 0);
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            XG[n * kLd + t * D + k] = a[k];
-            XG[(N + n) * kLd + t * D + k] = bb[k];
-        }
-    }
-    __syncthreads();
-    // G = (Kᵀa + dKᵀb)·Jᵀ  (trajectory.py:295)
-    if (valid) {
-        float G[D];
-        grad_exact<D>(P, XG + t * D, n, G);
-#pragma unroll
-        for (int k = 0; k < D; ++k) P.out1[(b * N + n) * D + k] = G[k];
-    }
-}
-
-// ------------------------------------------------------------- launchers
-// LDS of k_lean: the optimiser head + obstacles, no staged F fragments, the lean regions.
-inline size_t lean_lds(const KParams& p, bool help = false, bool bls = false, bool dense = false) {
-    KParams q = p;
-    q.regops = 1;
-    return (size_t)lean_extra(plan_lds(q, false, true, true).total, p.MP, p.NK, p.RP, p.nsplit, lean_vlds(p.NK, p.D, p.BT),
-                              p.D, help ? p.BT : 0, bls, dense).total * 4;
-}
-
-// The optimiser's control flow in LeanFlow terms (k_optimize runs every flow in one instantiation): the GD
-// single loop (dualOptimization = max_outer_iteration > 1, optimizer_GD.py:18) without extended-vis
-// snapshots is the bench flow; GD with snapshots or a dual loop, and BLS, the full flows.
-inline int optimizer_flow(const KParams& p) {
-    if (p.optimizer == IRM_OPT_BLS) return LF_BLS;
-    return (p.max_outer <= 1 && !p.record_series) ? LF_GD1 : LF_GD2;
-}
-// The lean kernel's control flow for a launch (-1: the general kernel serves it).
-inline int lean_flow(const KParams& p) { return p.lean_ok ? optimizer_flow(p) : -1; }
-// help: the launch's instantiation carries the BLS line-search helpers' exchange regions (lean_help), so
-// the check sees the LDS the launch will request (per-problem obstacle tables grow the base with TB·O)
-inline bool lean_fits(const KParams& p, bool help = false, bool bls = false) {
-    return (p.RP / 16) * p.nsplit <= p.BT / 64 && p.NK / 16 <= 4 * p.nsplit && lean_lds(p, help, bls) <= 160 * 1024;
-}
-
-// k_optimize<Shape> with the MAXT / operator-placement / optimiser variants (one shape per
-// instantiation unit, irm_opt_inst.hip).
-template <class Sh>
-hipError_t launch_general_shape(const KParams& p, hipStream_t s, LaunchDesc* desc);
-
-template <class Sh>
-inline int shape_name(char* buf, size_t n) {
-    if constexpr (Sh::kDense) return snprintf(buf, n, "DenseShape<%d,%d>", Sh::D, Sh::N);
-    else if constexpr (Sh::kNW > 0) return snprintf(buf, n, "FixShape<%d,%d,%d>", Sh::D, Sh::N, Sh::RP);
-    else return snprintf(buf, n, "DynShape<%d>", Sh::D);
-}
-inline const char* flow_name(int flow) { return flow == LF_GD1 ? "GD1" : flow == LF_GD2 ? "GD2" : "BLS"; }
-// What a k_lean launch records in `desc` besides run_optimizer's fields: the instantiation's name, its flow,
-// waypoints per lane and per-stage ranks (`queue`: the work queue's instantiation).
-template <class Sh>
-inline void describe_lean(LaunchDesc* desc, int tt, int wpl, bool full, int flow, bool queue) {
-    if (!desc) return;
-    char sn[48];
-    shape_name<Sh>(sn, sizeof(sn));
-    snprintf(desc->kernel, sizeof(desc->kernel), "k_lean<%s,%d,%d,%s,%s%s>", sn, tt, wpl, full ? "FULL" : "PART",
-             flow_name(flow), queue ? ",QUEUE" : "");
-    desc->lean = 1;
-    desc->flow = flow;
-    desc->wpl = wpl;
-    desc->rank_z = desc->rank_dir = 16;  // k_lean's per-stage ranks at RP = 32
-    desc->rank_g = 24;
-    if constexpr (Sh::kDense) {  // V_R = I: G is y'' and z is e' (no MFMAs), the direction at rank N
-        desc->rank_z = desc->rank_g = 0;
-        desc->rank_dir = Sh::RP;
-    }
-}
-
-// The one place an optimiser kernel is launched: records what runs in `desc` (irm_optimize_plan) and
-// launches unless desc->describe_only.
-template <class K>
-inline hipError_t run_optimizer(LaunchDesc* desc, K kernel, int grid, int threads, size_t lds, hipStream_t s,
-                                const KParams& p) {
-    if (desc) {
-        desc->grid = grid;
-        desc->threads = threads;
-        desc->lds_bytes = (int)lds;
-        desc->traj_per_block = p.TB;
-        if (desc->describe_only) return hipSuccess;
-    }
-    return launch_lds(kernel, grid, threads, lds, s, p);
-}
-
-template <class Sh, int TT, int WPL, bool FULL, int FLOW>
-hipError_t launch_lean_one(const KParams& p, int grid, hipStream_t s, LaunchDesc* desc) {
-    describe_lean<Sh>(desc, TT, WPL, FULL, FLOW, false);
-    return run_optimizer(desc, k_lean<Sh, TT, WPL, FULL, FLOW>, grid, p.BT,
-                         lean_lds(p, lean_help<Sh, TT, WPL, FULL, FLOW>(), FLOW == LF_BLS, Sh::kDense), s, p);
-}
-
-template <class Sh, int TT, int WPL, bool FULL>
-hipError_t launch_lean_flow(const KParams& p, int flow, int grid, hipStream_t s, LaunchDesc* desc) {
-    switch (flow) {
-        case LF_GD1: return launch_lean_one<Sh, TT, WPL, FULL, LF_GD1>(p, grid, s, desc);
-        case LF_GD2: return launch_lean_one<Sh, TT, WPL, FULL, LF_GD2>(p, grid, s, desc);
-        default: return launch_lean_one<Sh, TT, WPL, FULL, LF_BLS>(p, grid, s, desc);
-    }
-}
-
-// The work queue's instantiations k_lean<Sh, 256 / 512, 1, FULL, GD2 / BLS, QUE> (units of their own,
-// irm_opt_inst.hip IRM_INST_FIXQ_*): one waypoint per lane.
-template <class Sh>
-constexpr bool lean_queue_shape() {
-    if constexpr (Sh::kNW > 0 && !Sh::kDense && !Sh::kVariants)  // (a fixed shape: N is a constant)
-        return (Sh::D == 3 && (Sh::N == 50 || Sh::N == 64 || Sh::N == 128)) || (Sh::D == 7 && Sh::N == 128);
-    else
-        return false;
-}
-// Auto (irm_set_work_queue(ctx, -1)) selects the queue only where it measured faster than the static launch
-// by more than the spread of repeated launches (profiles/work_queue_ab.json): the C3 shape's
-// four-trajectory 512-thread workgroups, BLS −16 %, GD dual loop −7.5 % at B = 8,192.  (7-DoF N = 128 won
-// 7 % with two workgroups per CU and lost 35 % with one; it and the unmeasured shapes stay explicit.)
-constexpr bool lean_queue_auto(int D, int N, int threads, int flow) {
-    return D == 3 && N == 128 && threads == 512 && (flow == LF_BLS || flow == LF_GD2);
-}
-// Serves a launch whose context asks for the queue (p.queue_groups != 0) with G < `grid` persistent
-// workgroups: sets the problem counter to G·TB on the stream, then launches.  *served = false leaves the
-// launch to the static dispatch (the request covers every workgroup, auto does not select this flow).
-template <class Sh>
-hipError_t launch_lean_queue(const KParams& p, int flow, int grid, hipStream_t s, LaunchDesc* desc, bool* served);
-
-template <class Sh, int TT, int FLOW>
-hipError_t launch_lean_queue_flow(const KParams& p, int grid, hipStream_t s, LaunchDesc* desc, bool* served) {
-    auto kernel = k_lean<Sh, TT, 1, true, FLOW, true>;
-    const size_t lds = lean_lds(p, lean_help<Sh, TT, 1, true, FLOW>(), FLOW == LF_BLS, false);
-    int G = p.queue_groups;
-    if (G < 0) {  // auto: every CU full of resident workgroups, as the runtime counts them for this LDS request
-        if (!lean_queue_auto(Sh::D, Sh::N, TT, FLOW)) return hipSuccess;
-        hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        int per_cu = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, TT, lds);
-        if (e != hipSuccess) return e;
-        G = p.num_cus * per_cu;
-    }
-    if (G <= 0 || G >= grid || !p.queue) return hipSuccess;
-    *served = true;
-    describe_lean<Sh>(desc, TT, 1, true, FLOW, true);
-    if (desc) desc->queue_groups = G;
-    if (!desc || !desc->describe_only) {
-        const hipError_t e = hipMemsetD32Async((hipDeviceptr_t)p.queue, G * p.TB, 1, s);
-        if (e != hipSuccess) return e;
-    }
-    return run_optimizer(desc, kernel, G, p.BT, lds, s, p);
-}
-
-template <class Sh>
-hipError_t launch_lean_queue(const KParams& p, int flow, int grid, hipStream_t s, LaunchDesc* desc, bool* served) {
-    *served = false;
-    if (p.BT == 512) {
-        if (flow == LF_GD2) return launch_lean_queue_flow<Sh, 512, LF_GD2>(p, grid, s, desc, served);
-        if (flow == LF_BLS) return launch_lean_queue_flow<Sh, 512, LF_BLS>(p, grid, s, desc, served);
-    } else if (p.BT == 256) {
-        if (flow == LF_GD2) return launch_lean_queue_flow<Sh, 256, LF_GD2>(p, grid, s, desc, served);
-        if (flow == LF_BLS) return launch_lean_queue_flow<Sh, 256, LF_BLS>(p, grid, s, desc, served);
-    }
-    return hipSuccess;
-}
-// (the shapes of lean_queue_shape; build.py QUEUE_SHAPES.  Declared here so that the dispatch units call
-// the queue units' instantiations instead of compiling their own)
-#define IRM_QUEUE_SHAPES(X) X(3, 50) X(3, 64) X(3, 128) X(7, 128)
-#define IRM_EXTERN_FIXQ(D_, N_)                                                                                   \
-    extern template hipError_t launch_lean_queue<FixShape<D_, N_, 32>>(const KParams&, int, int, hipStream_t, \
-                                                                       LaunchDesc*, bool*);
-IRM_QUEUE_SHAPES(IRM_EXTERN_FIXQ)
-
-template <class Sh>
-hipError_t launch_optimize_shape(const KParams& p, hipStream_t s, LaunchDesc* desc) {
-    const int grid = (p.B + p.TB - 1) / p.TB;
-    if (grid <= 0) return hipSuccess;
-    return dispatch_t(p.BT, [&](auto tc) {
-        constexpr int TT = decltype(tc)::value;
-        const int flow = lean_flow(p);
-        if constexpr (!Sh::kVariants && TT == 512) {
-            if constexpr (Sh::kNW == 128) {
-                // diagnostic (IRM_LEAN_WPL=2): one wave per trajectory, two waypoints per lane
-                KParams q = p;
-                q.BT = p.BT / 2;
-                q.NW = p.NW / 2;
-                if (p.lean_wpl == 2 && flow == LF_GD1 && lean_fits(q))  // (GD only)
-                    return launch_lean_one<Sh, 256, 2, false, LF_GD1>(q, grid, s, desc);
-            }
-        }
-        if constexpr (!Sh::kVariants && TT <= 512) {  // the lean kernel (F operators register-resident:
-            // one stage-1 unit per wave; workgroups are padded to TT threads by choose_shape)
-            const bool help = flow == LF_BLS && lean_help<Sh, TT, 1, true, LF_BLS>();
-            if (flow >= 0 && p.BT == TT && lean_fits(p, help, flow == LF_BLS)) {
-                if constexpr (lean_queue_shape<Sh>()) {
-                    // the work queue, where the context asks for it (series launches keep the static launch)
-                    if (p.queue_groups != 0 && flow != LF_GD1 && !p.record_series) {
-                        bool served = false;
-                        const hipError_t e = launch_lean_queue<Sh>(p, flow, grid, s, desc, &served);
-                        if (served || e != hipSuccess) return e;
-                    }
-                }
-                return launch_lean_flow<Sh, TT, 1, true>(p, flow, grid, s, desc);
-            }
-        }
-        if constexpr (!Sh::kVariants && TT == 1024) {
-            if constexpr (Sh::kNW == 256 && Sh::D * 3 <= kCols) {  // ≥ 3 trajectories fit the MFMA columns
-                // N = 256 with more than two trajectories per workgroup: two waypoints per lane
-                KParams q = p;
-                q.BT = p.BT / 2;
-                q.NW = p.NW / 2;
-                if (flow >= 0 && lean_fits(q, false, flow == LF_BLS)) return launch_lean_flow<Sh, 512, 2, false>(q, flow, grid, s, desc);
-            }
-        }
-        return launch_general_shape<Sh>(p, s, desc);
-    });
-}
-
-// The general optimiser k_optimize<Shape, …> (every optimiser / control flow).  Instantiated in its
-// own unit (irm_opt_inst.hip, IRM_INST_GEN_*) so that build.py can compile it with the
-// iterative-ILP machine scheduler, which measured 10 % faster on it (faithful C3) while the lean
-// kernels keep the default scheduler.
-// The dense operator's k_lean (DenseShape, GD single loop, one 512-thread workgroup of TB trajectories):
-// *served = false leaves the launch to the general kernel (another workgroup size, LDS).
-template <class Sh>
-hipError_t launch_dense_shape(const KParams& p, hipStream_t s, LaunchDesc* desc, bool* served) {
-    *served = false;
-    if (p.BT != 512 || p.TB * Sh::D > kCols || lean_flow(p) != LF_GD1) return hipSuccess;
-    KParams q = p;
-    q.nsplit = 1;  // one split: every wave's stage-1 row tiles over the whole k range
-    if (lean_lds(q, false, false, true) > 160 * 1024) return hipSuccess;
-    *served = true;
-    const int grid = (p.B + p.TB - 1) / p.TB;
-    if (grid <= 0) return hipSuccess;
-    return launch_lean_one<Sh, 512, 1, true, LF_GD1>(q, grid, s, desc);
-}
-
-template <class Sh>
-hipError_t launch_general_shape(const KParams& p, hipStream_t s, LaunchDesc* desc) {
-    const bool stage = p.ops_in_lds != 0;
-    const Plan L = plan_lds(p, stage, true, false, Sh::kVariants && p.moving != 0, Sh::kVariants && p.via != 0);
-    const size_t lds = (size_t)L.total * 4;
-    const int grid = (p.B + p.TB - 1) / p.TB;
-    if (grid <= 0) return hipSuccess;
-    return dispatch_t(p.BT, [&](auto tc) {
-        constexpr int TT = decltype(tc)::value;
-        auto name = [&](bool ops_lds, bool regops, bool bls, bool full) {
-            if (!desc) return;
-            char sn[48];
-            shape_name<Sh>(sn, sizeof(sn));
-            snprintf(desc->kernel, sizeof(desc->kernel), "k_optimize<%s,%d,%s,%s,%s%s>", sn, TT,
-                     ops_lds ? "OPS_LDS" : "OPS_L2", regops ? "REGOPS" : "-", bls ? "BLS" : "GD", full ? ",FULL" : "");
-            desc->lean = 0;
-            desc->flow = optimizer_flow(p);
-            desc->wpl = 1;
-            desc->rank_z = desc->rank_dir = desc->rank_g = p.RP;
-            if (p.v_ident) desc->rank_g = desc->rank_z = 0;  // V_R = I: G is y'', z is e' (no MFMAs)
-        };
-        auto go = [&](auto bc) {
-            constexpr bool BB = decltype(bc)::value;
-            if constexpr (TT <= 512) {
-                if constexpr (!Sh::kVariants) {
-                    if (p.regops && p.BT == TT) {
-                        name(true, true, BB, true);
-                        return run_optimizer(desc, k_optimize<Sh, TT, true, true, BB, true>, grid, p.BT, lds, s, p);
-                    }
-                }
-                if (p.regops) {
-                    name(true, true, BB, false);
-                    return run_optimizer(desc, k_optimize<Sh, TT, true, true, BB>, grid, p.BT, lds, s, p);
-                }
-            }
-            name(stage, false, BB, false);
-            return stage ? run_optimizer(desc, k_optimize<Sh, TT, true, false, BB>, grid, p.BT, lds, s, p)
-                         : run_optimizer(desc, k_optimize<Sh, TT, false, false, BB>, grid, p.BT, lds, s, p);
-        };
-        return p.optimizer == IRM_OPT_BLS ? go(std::integral_constant<bool, true>{})
-                                          : go(std::integral_constant<bool, false>{});
-    });
-}
-
-template <int D>
-hipError_t launch_forward_dim(const KParams& p, int mode, hipStream_t s) {
-    const Plan L = plan_lds(p, false, false, false, p.moving != 0, p.via != 0);
-    const size_t lds = (size_t)L.total * 4;
-    const int grid = (p.B + p.TB - 1) / p.TB;
-    if (grid <= 0) return hipSuccess;
-    return dispatch_t(p.BT, [&](auto tc) {
-        constexpr int TT = decltype(tc)::value;
-        return launch_lds(k_forward<D, TT>, grid, p.BT, lds, s, p, mode);
-    });
-}
-
 }  // namespace irm
+
+// the kernels and launchers in headers of their own (they follow the optimiser kernels they launch)
+#include "irm_k_forward.hpp"  // k_forward: the α-space evaluation kernel
+#include "irm_launch.hpp"     // the per-shape launchers

@@ -348,6 +348,11 @@ __host__ __device__ inline LeanX lean_extra(int base, int MP, int NK, int RP, in
 // V_R fragments staged in LDS for the lean kernel: N ≤ 128 at D ≤ 3 in 512-thread workgroups (117 KiB
 // at N = 128).  256-thread workgroups run two per CU (76 KiB each without them) and every N = 256
 // shape reads them from L2 instead: LDS budget.
+// The lean evaluations (irm_physics.hpp, LEAN) keep zm / zvm for the gradient inputs at D ≤ 3; at D = 7 the 14
+// values live across the evaluation barrier pushed the spill-free 7-DoF bench kernels into scratch, so the
+// gradient inputs recompute them there
+template <int D>
+constexpr bool kLeanKeep = D <= 3;
 __host__ __device__ constexpr bool lean_vlds(int NK, int D, int threads) { return NK <= 128 && D <= 3 && threads > 256; }
 
 // Stage-1 split-K factor: units of 4 k-quads over the position half.

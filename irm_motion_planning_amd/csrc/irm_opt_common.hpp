@@ -1,7 +1,7 @@
 // irm_opt_common.hpp — what both optimiser kernels share: the evaluation's wave reduction (ered_store), the
 // reference's fp32 α update with its rounding residual (alpha_step*), the IEEE quotient in three VALU
 // (rcp_refined, div_rcp, rcp_rn_of), ld_frag and the problem shapes (FixShape, DenseShape, DynShape).
-// Included by irm_kernels_impl.hpp and by irm_kernels.hip (the shapes it dispatches on).
+// Included by irm_kernels_impl.hpp, irm_lean_plan.hpp and by irm_kernels.hip (the shapes it dispatches on).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -128,22 +128,12 @@ __device__ __forceinline__ float alpha_step(float al, float c, float lr, float g
 // e' = −(α' − (c·α − lr·G))/lr = (c·α − α')/lr − G, as u = fl(c·α − α') (one rounding, |u| ≈ |lr·G|) and
 // e' = fl(u·(1/lr) − G) (ne = −1/lr): the residual to 2^-24 of |G| (i.e. the waypoint state to 2^-24 of a
 // step per step, below the rank-16 direction's own 1.5e-7) in two FMAs instead of TwoSum and the two
-// product errors (alpha_step_gd: 9 more VALU per component on the round's critical path)
+// product errors (alpha_step's form: 9 more VALU per component on the round's critical path)
 __device__ __forceinline__ float alpha_step_gd2(float al, float c, float lr, float G, float ne, float& eo) {
     const float p1 = unfused(c * al), p2 = unfused(lr * G);
     const float an = unfused(p1 - p2);
     const float u = fmaf(c, al, -an);
     eo = fmaf(-u, ne, -G);
-    return an;
-}
-__device__ __forceinline__ float alpha_step_gd(float al, float c, float lr, float G, float& e) {
-    const float p1 = unfused(c * al), p2 = unfused(lr * G);
-    const float an = unfused(p1 - p2);
-    const float ep1 = fmaf(c, al, -p1);
-    const float bb = an - p1;
-    const float es = (p1 - (an - bb)) + (-p2 - bb);
-    const float ep = fmaf(lr, G, -p2);                  // lr·G − p2
-    e = ((-es) + ep) - ep1;
     return an;
 }
 

@@ -119,11 +119,8 @@ __device__ __forceinline__ void via_row_terms(const KParams& P, size_t b, int co
 // returned as w.jx (with w.gx = 1, w.jy = w.gy = 0) so grad_waypoint is shared.
 // POT = false (end-effector cost only): everything but the obstacle potential, whose inputs are left
 // in w.fx / w.fy (potential_pair evaluates two waypoints' potentials in one pass over the obstacles).
-// LEAN evaluations keep zm / zvm for the gradient inputs at D ≤ 3; at D = 7 the 14 values live across
-// the evaluation barrier pushed the spill-free 7-DoF bench kernels into scratch, so the gradient inputs
-// recompute them there (lean_pen: the same arithmetic, the same values)
-template <int D>
-constexpr bool kLeanKeep = D <= 3;
+// LEAN evaluations keep zm / zvm for the gradient inputs where kLeanKeep<D> (irm_layout.hpp); elsewhere the
+// gradient inputs recompute them (lean_pen: the same arithmetic, the same values)
 template <int D>
 __device__ __forceinline__ void lean_pen(const KParams& P, const float (&q)[D], const float (&v)[D], float (&zm)[D],
                                          float (&zvm)[D]) {

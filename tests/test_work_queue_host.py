@@ -88,11 +88,20 @@ def test_queue_units_are_built():
         assert flags == [f"-DIRM_INST_FIXQ_D={d}", f"-DIRM_INST_FIXQ_N={n}"]
         assert (d, n) in build.FIX_SHAPES  # the dispatch unit that calls it
         assert not any("FIXQ" in f for f in units[f"opt_fix{d}_{n}"][2])
-    # the shape list of the kernels' header and the build's agree
-    hpp = open(os.path.join(build.CSRC, "irm_kernels_impl.hpp")).read()
-    m = re.search(r"#define IRM_QUEUE_SHAPES\(X\)(.*)", hpp)
-    assert m and sorted(map(tuple, (map(int, p) for p in re.findall(r"X\((\d+),\s*(\d+)\)", m.group(1))))) == \
-        sorted(build.QUEUE_SHAPES)
+    # the shape lists of the launchers' header and the build's agree, family by family
+    hpp = open(os.path.join(build.CSRC, "irm_launch_decl.hpp")).read()
+    for macro, shapes in (("IRM_QUEUE_SHAPES", build.QUEUE_SHAPES), ("IRM_FIX_SHAPES", build.FIX_SHAPES),
+                          ("IRM_DENSE_SHAPES", build.DENSE_SHAPES)):
+        m = re.search(r"#define %s\(X\)(.*)" % macro, hpp)
+        assert m and sorted(map(tuple, (map(int, p) for p in re.findall(r"X\((\d+),\s*(\d+)\)", m.group(1))))) == \
+            sorted(shapes), macro
+    m = re.search(r"#define IRM_DYN_DIMS\(X\)(.*)", hpp)
+    assert m and [int(d) for d in re.findall(r"X\((\d+)\)", m.group(1))] == list(range(1, build.MAX_D + 1))
+    # each list is written once: no other file under csrc/ defines or repeats one
+    for f in os.listdir(build.CSRC):
+        if f != "irm_launch_decl.hpp":
+            assert not re.search(r"#define IRM_(QUEUE_SHAPES|FIX_SHAPES|DENSE_SHAPES|DYN_DIMS)\b",
+                                 open(os.path.join(build.CSRC, f)).read()), f
     # and the build id moves with them: a unit list without the queue units hashes differently
     full = build.source_hash()
     orig = build._units

@@ -4,7 +4,7 @@ from each tree's csrc/ (the unit's name as its compilation-unit id, so that the 
 drops the .ident line and compares the two files byte for byte.  One line per unit:
 `identical`, or the first differing line; exit status 1 on any difference.  A unit whose source only one of the
 trees has (a unit the change adds) is named as such and is no difference.  The check for a change that
-only moves or tidies kernel source (profiles/header_split_isa.txt, profiles/dense_sample_split_isa.txt).
+only moves or tidies kernel source (profiles/header_split_isa.txt, profiles/dense_sample_split_isa.txt, profiles/kernel_split_isa.txt).
 
     python tools/isa_same.py TREE_A TREE_B [--extra "FLAGS"] [-j 8]
 
