@@ -590,6 +590,102 @@ int irm_optimize_batch_via_dev(irm_ctx* ctx, const irm_batch_dev* args, const fl
 int irm_optimize_plan_via(const irm_ctx* ctx, int32_t batch, int32_t n_obstacles, int32_t record_series,
                           irm_launch_plan* out, const irm_via* via);
 
+/* Multi-start planning: seed ensembles ranked and gathered on the device.  One optimize call is one descent from
+ * one seed in a landscape that is not convex; a multi-start call runs S seeds per problem in one launch and keeps
+ * the best by a stated order.  Candidates are rows, problem-major: candidate s of problem b is row b·S + s,
+ * 1 ≤ S ≤ IRM_MAX_SEEDS.
+ *
+ * The ensemble.  Candidate 0 is the α of the straight-line initialisation, bit for bit (the expression
+ * α0 = u⊗(s·J⁻¹) + w⊗(g·J⁻¹) of Trajectory.initTrajectory as this library evaluates it); its waypoints output is
+ * the plain line, base below.  Candidate s ≥ 1 has the waypoints, fp32, for support row n and joint d
+ *   base = fmaf(c_n, goal_d − start_d, start_d)          c_n: the smooth step 6t⁵ − 15t⁴ + 10t³ of the support time
+ *                                                        t_n, the fp32 table the operator build forms
+ *   q    = fmaf(φ_n, a, base)                            φ_n = 16·(p·p), p = t_n·(1 − t_n), fp32: value and slope 0
+ *                                                        at both ends, peak 1; a host-built table, uploaded once
+ *   q    = min(max(q, lo), hi)                           lo / hi = joint_safety_limit·min / max_joint_position, the
+ *                                                        bounds the IK seed clamps to
+ * and its α is the ridge fit's arithmetic on these waypoints (Fitting and re-timing above: the same fp64 FMA chains,
+ * the same W, one rounding), so it is bit-identical to the fit of the waypoints output.  The amplitude is
+ *   a = fmaf(2A, U, −A),  U = (h >> 8)·2⁻²⁴ (exact in fp32),
+ *   h = fmix32(fmix32(fmix32(fmix32(seed ^ 0x243F6A88) + (problem_offset + b)) + s) + d)
+ * in uint32 arithmetic, fmix32 being MurmurHash3's finaliser (h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13;
+ * h *= 0xC2B2AE35; h ^= h >> 16).  A candidate depends on (seed, problem_offset + b, s, d) and its problem's start
+ * and goal only — not on S, the batch or the rest of it: ensembles nest (the first 4 candidates of 8 are the 4 of 4)
+ * and a shard that passes its first problem's global index as problem_offset reproduces the unsharded rows.
+ * A = 0 gives S copies of the clamped line behind candidate 0.
+ *
+ * The ranking.  The key of a candidate is (class, loss, s), compared lexicographically:
+ *   class = 2·(constraints_ok == 0) + (n_colliding > 0)     (without reports: 2·(constraints_ok == 0))
+ *   loss  = final_loss; a NaN loss puts the candidate in class 4 with its loss compared as +INFINITY
+ *   ties go to the lower s (−0 and +0 compare equal)
+ * rank[b·S + s] is the position of candidate s in its problem's order (a permutation of 0 … S−1) and winner[b] the
+ * candidate at position 0.  One wave per problem, one lane per candidate.
+ *
+ * The call.  On one stream: seeds → the per-problem rows (start, goal, goal_xy, per-problem obstacle, velocity and
+ * radius tables) replicated S times → the existing optimiser launch of irm_optimize_batch_dev (its _moving / _task
+ * twin with a velocity table / goal_xy) on the B·S problems with alpha0 = the seeds → with rank_clearance the
+ * existing clearance check on the B·S results → ranking → the winner's rows gathered into the B-sized outputs.
+ * Every candidate is therefore, to the bit, the plain optimize of its replicated problem from its seed, its report
+ * the plain clearance check of its α, and n_seeds = 1 is the plain optimize from the straight-line α.  With goal_xy
+ * and a NULL goal the goal configuration (of every candidate) is the IK seed's for (start, goal_xy).
+ * IRM_EINVAL (with a message naming the argument): n_seeds outside [1, IRM_MAX_SEEDS]; a negative or non-finite
+ * amplitude; a negative problem_offset; rank_clearance without an evaluation grid; obstacle_radius or a non-zero
+ * link_radius without rank_clearance; alpha0 (the seeds are the call's own); series recording (series_out, or a
+ * context that records); a workspace smaller than the sizing function's answer.  Via-points have no multi-start form:
+ * the via seed is a path of its own.
+ * The _dev forms only enqueue and allocate nothing (the first seed call on a context uploads the fit operator and
+ * the c / φ tables before it enqueues): the caller passes workspace_bytes ≥ the sizing function's answer for the same
+ * batch, n_seeds, n_obstacles and obstacle_stride, 256-byte aligned.  Outputs must not overlap inputs or the
+ * workspace.  Additive symbols: IRM_ABI_VERSION stays 3 and no struct changes layout; no reference counterpart. */
+#define IRM_MAX_SEEDS 64
+typedef struct irm_multistart {
+    int32_t n_seeds;               /* S */
+    uint32_t seed;
+    float amplitude;               /* A ≥ 0, finite: the bump amplitudes are uniform in [−A, A) */
+    int32_t problem_offset;        /* global index of this call's problem 0 (a shard's offset), ≥ 0 */
+    int32_t rank_clearance;        /* 1: run the clearance check on every candidate and rank with n_colliding */
+    float link_radius;             /* of the clearance check */
+    const float* obstacle_radius;  /* of the clearance check, nullable: O shared, or per problem at obstacle_stride/2
+                                      (host pointer; device pointer in the _dev form) */
+} irm_multistart;
+/* What a multi-start call returns beside the winner's rows; every pointer but winner nullable (host pointers; device
+ * pointers in the _dev form). */
+typedef struct irm_multistart_out {
+    int32_t* winner;                     /* B */
+    float* cand_alpha;                   /* B·S×N×D */
+    float* cand_traj;                    /* B·S×N×D */
+    irm_stats* cand_stats;               /* B·S */
+    irm_clearance_report* cand_reports;  /* B·S; written with rank_clearance only */
+    int32_t* rank;                       /* B·S */
+} irm_multistart_out;
+/* alpha_out B·S×N×D; waypoints_out B·S×N×D, nullable.  batch = 0 is a no-op. */
+int irm_seed_ensemble(irm_ctx* ctx, const float* start, const float* goal, int32_t batch, int32_t n_seeds,
+                      uint32_t seed, float amplitude, int32_t problem_offset, float* alpha_out, float* waypoints_out);
+int irm_seed_ensemble_dev(irm_ctx* ctx, const float* start_dev, const float* goal_dev, int32_t batch, int32_t n_seeds,
+                          uint32_t seed, float amplitude, int32_t problem_offset, float* alpha_dev,
+                          float* waypoints_dev, void* stream);
+/* stats B·S, reports B·S (nullable); winner_out B, rank_out B·S (nullable). */
+int irm_rank_candidates(irm_ctx* ctx, const irm_stats* stats, const irm_clearance_report* reports, int32_t batch,
+                        int32_t n_seeds, int32_t* winner_out, int32_t* rank_out);
+int irm_rank_candidates_dev(irm_ctx* ctx, const irm_stats* stats_dev, const irm_clearance_report* reports_dev,
+                            int32_t batch, int32_t n_seeds, int32_t* winner_dev, int32_t* rank_dev, void* stream);
+/* Bytes of device workspace of the _dev call below (every optional table and output counted); negative IRM_E* code
+ * on failure. */
+int64_t irm_multistart_workspace(const irm_ctx* ctx, int32_t batch, int32_t n_seeds, int32_t n_obstacles,
+                                 int32_t obstacle_stride);
+/* The arguments of irm_optimize_batch_task behind the descriptor (alpha0 and series_out must be NULL); alpha_out,
+ * traj_out, stats_out: the winner's rows (B), each nullable; out->winner B. */
+int irm_optimize_multistart(irm_ctx* ctx, const irm_multistart* ms, const float* alpha0, const float* start,
+                            const float* goal, const float* obstacles, int32_t n_obstacles, int32_t obstacle_stride,
+                            int32_t batch, float* alpha_out, float* traj_out, irm_stats* stats_out, float* series_out,
+                            const float* obstacle_velocity, const float* goal_xy, const irm_multistart_out* out);
+/* Device pointers, enqueue-only on `stream`: args as irm_optimize_batch_dev takes it (batch = B; alpha0 and
+ * series_out 0; goal may be 0 with goal_xy_dev); the two structs are read on the host, during the call. */
+int irm_optimize_multistart_dev(irm_ctx* ctx, const irm_multistart* ms, const irm_batch_dev* args,
+                                const float* obstacle_velocity_dev, const float* goal_xy_dev,
+                                const irm_multistart_out* out, void* workspace_dev, int64_t workspace_bytes,
+                                void* stream);
+
 /* Build id of the library: the first 16 hex digits of the SHA-256 over every file of
  * irm_motion_planning_amd/csrc and include/irm.h, the compile flags of every unit and the build
  * variant (build.py source_hash); "unknown" otherwise.

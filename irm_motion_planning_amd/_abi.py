@@ -9,6 +9,7 @@ import ctypes
 import os
 
 from . import clearance as _clearance  # irm_clearance_report's mirror
+from . import multistart as _multistart  # irm_multistart's and irm_multistart_out's mirrors
 from . import via as _via  # irm_via's mirror lives with the via-point value object
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -230,6 +231,21 @@ PROTOTYPES = {
     "irm_clearance_dev": (ctypes.c_int, _CLEARANCE + [_h]),
     "irm_ik_seed": (ctypes.c_int, [_h, c_float_p, c_float_p, _i32, c_float_p, c_float_p]),
     "irm_ik_seed_dev": (ctypes.c_int, [_h, c_float_p, c_float_p, _i32, c_float_p, c_float_p, _h]),
+    # multi-start planning: seed ensembles, ranking, and the call (descriptor, irm_optimize_batch_task's arguments,
+    # the candidates' outputs; the _dev form: irm_batch_dev, the two tables, outputs, workspace, its bytes, stream)
+    "irm_seed_ensemble": (ctypes.c_int, [_h, c_float_p, c_float_p, _i32, _i32, ctypes.c_uint32, _f, _i32, c_float_p,
+                                         c_float_p]),
+    "irm_seed_ensemble_dev": (ctypes.c_int, [_h, c_float_p, c_float_p, _i32, _i32, ctypes.c_uint32, _f, _i32, c_float_p,
+                                             c_float_p, _h]),
+    "irm_rank_candidates": (ctypes.c_int, [_h, ctypes.POINTER(IrmStats), ctypes.POINTER(_clearance.IrmClearanceReport),
+                                           _i32, _i32, c_int32_p, c_int32_p]),
+    "irm_rank_candidates_dev": (ctypes.c_int, [_h, _h, _h, _i32, _i32, _h, _h, _h]),
+    "irm_multistart_workspace": (ctypes.c_int64, [_h, _i32, _i32, _i32, _i32]),
+    "irm_optimize_multistart": (ctypes.c_int, [_h, ctypes.POINTER(_multistart.IrmMultistart)] + _OPTIMIZE[1:] +
+                                [c_float_p, c_float_p, ctypes.POINTER(_multistart.IrmMultistartOut)]),
+    "irm_optimize_multistart_dev": (ctypes.c_int, [_h, ctypes.POINTER(_multistart.IrmMultistart),
+                                                   ctypes.POINTER(IrmBatchDev), c_float_p, c_float_p,
+                                                   ctypes.POINTER(_multistart.IrmMultistartOut), _h, ctypes.c_int64, _h]),
     "irm_build_id": (ctypes.c_char_p, []),
     "irm_debug_phase_profile": (ctypes.c_int, [_h, ctypes.POINTER(ctypes.c_uint64), _i32]),
     "irm_debug_bls_trace_enable": (ctypes.c_int, [_h, _i32]),

@@ -56,6 +56,16 @@ class _PersistentOptimizer:
         if self.via is not None:
             print("via-points at support rows", self.via.rows, "of", self.context.N,
                   "(times", [float(t) for t in np.round(np.asarray(self.via.rows) / (self.context.N - 1), 4)], ")")
+        # --multi-start S: every optimize() runs S seeds per problem and keeps the best (Context.optimize_multistart);
+        # with --clearance M the candidates are ranked with the clearance check on linspace(0, 1, M) (0: off — the
+        # calls below are then the existing ones)
+        self.multi_start = int(getattr(args, "multi_start", 0) or 0)
+        self.last_multistart = None
+        if self.multi_start:
+            if self.via is not None or self.extendedVis or getattr(args, "coarse_n_timesteps", 0) > 0:
+                raise ValueError("--multi-start does not combine with via-points, --extended-vis or --coarse-n-timesteps")
+            if getattr(args, "clearance", 0) > 0:
+                self.context.set_eval_times(np.linspace(0, 1, args.clearance, dtype=np.float32))
         self.last_stats = None
         self.last_profile = {}
         t1 = time.time()
@@ -64,8 +74,28 @@ class _PersistentOptimizer:
         print("setup object, jit-compile took", 1000 * (t2 - t1), "ms")
 
     # ------------------------------------------------------------------ API
+    def _multistart(self, start, goal, obstacles, vel, goal_xy, problem_offset=0):
+        """optimize() through --multi-start: (alpha, traj, stats); self.last_multistart keeps the winner and the
+        candidate table."""
+        a = self.args
+        ranked = getattr(a, "clearance", 0) > 0
+        alpha, traj, stats, info = self.context.optimize_multistart(
+            start, goal, obstacles, self.multi_start, seed=getattr(a, "multi_start_seed", 0),
+            amplitude=getattr(a, "multi_start_amplitude", 1.0), problem_offset=problem_offset, rank_clearance=ranked,
+            obstacle_radius=a.obstacle_radius if ranked else None, link_radius=a.link_radius if ranked else 0.0,
+            obstacle_velocity=vel, goal_xy=goal_xy, candidates=True)
+        self.last_multistart = info
+        return alpha, traj, stats
+
     def optimize(self):
         t0 = time.perf_counter()
+        if self.multi_start:
+            alpha, traj, stats = self._multistart(self.env.start_config, self.env.goal_config, self.env.obstacles,
+                                                  self.obstacle_velocity, self.goal_xy)
+            self.last_profile = {"optimize_ms": 1000 * (time.perf_counter() - t0)}
+            self.last_stats = stats
+            self.last_trajectory = traj
+            return alpha
         res = self.context.optimize(self.env.start_config, self.env.goal_config, self.env.obstacles,
                                     series=self.extendedVis, obstacle_velocity=self.obstacle_velocity,
                                     goal_xy=self.goal_xy, via=self.via)
@@ -103,7 +133,8 @@ class _PersistentOptimizer:
                             "fine": {"n_timesteps": self.context.N, "alpha0": alpha0, "stats": res[2]}}
         return res
 
-    def optimize_batch(self, start, goal, obstacles=None, alpha0=None, obstacle_stride=0, series=False, goal_xy=None):
+    def optimize_batch(self, start, goal, obstacles=None, alpha0=None, obstacle_stride=0, series=False, goal_xy=None,
+                       problem_offset=0):
         """Batched optimize(): B independent start/goal problems (B×D each); goal_xy (B×2): end-effector
         targets instead of the goal configurations (which then only shape the initial line).
 
@@ -113,6 +144,11 @@ class _PersistentOptimizer:
         obstacles = self.env.obstacles if obstacles is None else obstacles
         start = np.asarray(start, np.float32).reshape(-1, self.trajectory.robot.N_joints)
         goal = np.asarray(goal, np.float32).reshape(-1, self.trajectory.robot.N_joints)
+        if self.multi_start and alpha0 is None and not series:
+            # problem_offset: the global index of start[0] (a shard's offset: the seeds then do not depend on the sharding)
+            res = self._multistart(start, goal, obstacles, vel, goal_xy, problem_offset)
+            self.last_stats = res[2]
+            return res
         res = self.context.optimize(start, goal, obstacles, alpha0=alpha0, obstacle_stride=obstacle_stride,
                                     series=series, obstacle_velocity=vel, goal_xy=goal_xy, via=self.via)
         self.last_stats = res[2]

@@ -12,9 +12,19 @@ import numpy as np
 from . import _abi
 from ._abi import IrmBatchDev, IrmDenseReport, IrmInfo, IrmLaunchPlan, IrmParams, IrmStats, check, load_library
 from .clearance import CLEARANCE_REPORT_FIELDS, IrmClearanceReport
+from .multistart import IRM_MAX_SEEDS, IrmMultistart, IrmMultistartOut
 from .via import IrmVia, ViaPoints
 
 _fp = _abi.c_float_p
+
+
+def _struct_dtype(cls):
+    """The numpy record dtype of a ctypes struct of float / int32 fields."""
+    return np.dtype([(name, np.float32 if ctype is ctypes.c_float else np.int32) for name, ctype in cls._fields_])
+
+
+_STATS_DTYPE = _struct_dtype(IrmStats)
+_REPORT_DTYPE = _struct_dtype(IrmClearanceReport)
 
 
 def _f32(a):
@@ -598,6 +608,171 @@ class Context:
         if series:
             return alpha, traj, st, ser
         return alpha, traj, st
+
+    # ------------------------------------------------------ multi-start planning
+    def seed_ensemble(self, start, goal, n_seeds, seed=0, amplitude=1.0, problem_offset=0, with_waypoints=False):
+        """The S seeds of every problem (irm_seed_ensemble): α of shape (B, S, N, D) — candidate 0 is init_alpha's α
+        to the bit, candidate s ≥ 1 the fit of the smooth-step line plus a hashed smooth bump of amplitude up to
+        `amplitude` per joint, clamped to the joint range.  A candidate depends on (seed, problem_offset + b, s)
+        and its problem's start and goal only.  with_waypoints: also the waypoints the seeds were fitted to,
+        (B, S, N, D).  A single start (D,) gives (S, N, D)."""
+        s, single = self._batch(start, (self.D,))
+        B, S = s.shape[0], int(n_seeds)
+        g = _f32(np.broadcast_to(_f32(goal), (B, self.D)))
+        rows = B * max(S, 0)
+        alpha = np.zeros((rows, self.N, self.D), np.float32)
+        way = np.zeros_like(alpha) if with_waypoints else None
+        check(self.lib.irm_seed_ensemble(self._h, _ptr(s), _ptr(g), B, S, int(seed) & 0xFFFFFFFF, float(amplitude),
+                                         int(problem_offset), _ptr(alpha), _ptr(way)))
+        shape = ((S,) if single else (B, S)) + (self.N, self.D)
+        alpha = alpha.reshape(shape)
+        return (alpha, way.reshape(shape)) if with_waypoints else alpha
+
+    def rank_candidates(self, stats, reports=None, n_seeds=None):
+        """Rank B·S candidates per problem by the key (class, loss, s) (irm_rank_candidates).  stats: a dict with
+        constraints_ok and final_loss, each (B, S) or (B·S,) with n_seeds; reports (optional): a dict with
+        n_colliding of the same shape, or that array.  Returns (winner (B,), rank (B, S))."""
+        ok = np.asarray(stats["constraints_ok"])
+        if n_seeds is None:
+            if ok.ndim != 2:
+                raise ValueError("rank_candidates() needs n_seeds for flat (B*S,) tables")
+            n_seeds = ok.shape[1]
+        S = int(n_seeds)
+        ok = ok.reshape(-1)
+        loss = np.asarray(stats["final_loss"], np.float32).reshape(-1)
+        if S < 1 or ok.shape[0] % S or loss.shape != ok.shape:
+            raise ValueError(f"stats of {ok.shape[0]} / {loss.shape[0]} candidates do not divide into n_seeds={S}")
+        BS = ok.shape[0]
+        B = BS // S
+        st = (IrmStats * max(BS, 1))()
+        recs = np.frombuffer(st, dtype=_STATS_DTYPE)
+        recs["constraints_ok"][:BS] = ok.astype(np.int32)
+        recs["final_loss"][:BS] = loss
+        rp = None
+        if reports is not None:
+            ncol = np.asarray(reports["n_colliding"] if isinstance(reports, dict) else reports).reshape(-1)
+            if ncol.shape[0] != BS:
+                raise ValueError(f"reports of {ncol.shape[0]} candidates, stats of {BS}")
+            rp = (IrmClearanceReport * max(BS, 1))()
+            np.frombuffer(rp, dtype=_REPORT_DTYPE)["n_colliding"][:BS] = ncol.astype(np.int32)
+        winner = np.zeros(B, np.int32)
+        rank = np.zeros((B, S), np.int32)
+        check(self.lib.irm_rank_candidates(self._h, st, rp, B, S, winner.ctypes.data_as(_abi.c_int32_p),
+                                           rank.ctypes.data_as(_abi.c_int32_p)))
+        return winner, rank
+
+    def optimize_multistart(self, start, goal, obstacles, n_seeds, seed=0, amplitude=1.0, problem_offset=0,
+                            rank_clearance=False, obstacle_radius=None, link_radius=0.0, obstacle_velocity=None,
+                            goal_xy=None, candidates=False, via=None, series=False):
+        """optimize() from S seeds per problem, ranked and gathered on the device (irm_optimize_multistart): the
+        seeds of seed_ensemble, the plain optimiser launch on the B·S replicated problems, with rank_clearance the
+        clearance check of every candidate on the evaluation times (set_eval_times; obstacle_radius / link_radius
+        as Context.clearance takes them), the ranking by (class, loss, s) and the winner's rows.
+        Returns (alpha, traj, stats, info): the winner's α, trajectory and statistics per problem; info["winner"]
+        (B,) and, with candidates=True, info["alpha"], info["traj"] (B, S, N, D), info["stats"] (a dict of (B, S)
+        arrays), info["rank"] (B, S) and with rank_clearance info["reports"] (a dict of (B, S) arrays).
+        goal=None with goal_xy: the goal configuration is ik_seed(start, goal_xy), as in optimize().  Via-points and
+        series recording have no multi-start form (IrmError)."""
+        if self._has_via(via):
+            raise _abi.IrmError("irm error -22: via: via-points have no multi-start form (the via seed is a path of its own)")
+        s, single = self._batch(start, (self.D,))
+        B, S = s.shape[0], int(n_seeds)
+        gxy = None if goal_xy is None else self._goal_xy(goal_xy, B)
+        g = None if goal is None else _f32(np.broadcast_to(_f32(goal), (B, self.D)))
+        obs, O, stride = self._obstacle_table(obstacles, B)
+        vel = None if obstacle_velocity is None else self._velocity(obstacle_velocity, obs)
+        rad = None
+        if obstacle_radius is not None and O > 0:
+            want = (B, O) if stride else (O,)
+            try:
+                rad = _f32(np.broadcast_to(_f32(obstacle_radius), want))
+            except ValueError:
+                raise ValueError(f"obstacle_radius must broadcast to {want}, got {np.shape(obstacle_radius)}") from None
+        ms = IrmMultistart()
+        ms.n_seeds, ms.seed, ms.amplitude = S, int(seed) & 0xFFFFFFFF, float(amplitude)
+        ms.problem_offset, ms.rank_clearance = int(problem_offset), int(bool(rank_clearance))
+        ms.link_radius = float(link_radius)
+        ms.obstacle_radius = None if rad is None else rad.ctypes.data
+        rows = B * min(max(S, 0), IRM_MAX_SEEDS)
+        alpha = np.zeros((B, self.N, self.D), np.float32)
+        traj = np.zeros_like(alpha)
+        stats = (IrmStats * max(B, 1))()
+        winner = np.zeros(B, np.int32)
+        out = IrmMultistartOut()
+        out.winner = winner.ctypes.data
+        ser = np.zeros(4, np.float32) if series else None  # (refused by the library: it names the argument)
+        if candidates:
+            c_alpha = np.zeros((rows, self.N, self.D), np.float32)
+            c_traj = np.zeros_like(c_alpha)
+            c_stats = (IrmStats * max(rows, 1))()
+            c_rep = (IrmClearanceReport * max(rows, 1))()
+            c_rank = np.zeros(rows, np.int32)
+            out.cand_alpha, out.cand_traj, out.rank = c_alpha.ctypes.data, c_traj.ctypes.data, c_rank.ctypes.data
+            out.cand_stats, out.cand_reports = ctypes.addressof(c_stats), ctypes.addressof(c_rep)
+        check(self.lib.irm_optimize_multistart(self._h, ctypes.byref(ms), None, _ptr(s), _ptr(g), _ptr(obs), O, stride, B,
+                                               _ptr(alpha), _ptr(traj), stats, _ptr(ser), _ptr(vel), _ptr(gxy),
+                                               ctypes.byref(out)))
+        st = stats_to_dict(stats[:B])
+        info = {"winner": winner, "n_seeds": S}
+        if candidates:
+            shape = (B, S)
+            recs = np.frombuffer(c_stats, dtype=_STATS_DTYPE)[:rows]
+            info["alpha"], info["traj"] = c_alpha.reshape(shape + (self.N, self.D)), c_traj.reshape(shape + (self.N, self.D))
+            info["stats"] = {name: recs[name].copy().reshape(shape) for name in _abi.STATS_FIELDS}
+            info["rank"] = c_rank.reshape(shape)
+            if rank_clearance:
+                rep = _report(c_rep, CLEARANCE_REPORT_FIELDS, ("collision_free",), False)
+                info["reports"] = {k: v[:rows].reshape(shape) for k, v in rep.items()}
+        if single:
+            alpha, traj = alpha[0], traj[0]
+            st = {k: v[0] for k, v in st.items()}
+            info = {k: (v[0] if isinstance(v, np.ndarray) else {n: a[0] for n, a in v.items()} if isinstance(v, dict) else v)
+                    for k, v in info.items()}
+        return alpha, traj, st, info
+
+    def multistart_workspace(self, batch, n_seeds, n_obstacles=0, obstacle_stride=0):
+        """Bytes of device workspace optimize_multistart_dev needs (irm_multistart_workspace)."""
+        n = int(self.lib.irm_multistart_workspace(self._h, int(batch), int(n_seeds), int(n_obstacles), int(obstacle_stride)))
+        if n < 0:
+            check(n)
+        return n
+
+    def seed_ensemble_dev(self, start_dev, goal_dev, batch, n_seeds, alpha_dev, seed=0, amplitude=1.0, problem_offset=0,
+                          waypoints_dev=0, stream=0):
+        """Enqueue irm_seed_ensemble_dev with raw device addresses; waypoints_dev 0: no waypoints output."""
+        check(self.lib.irm_seed_ensemble_dev(self._h, _dev(start_dev), _dev(goal_dev), int(batch), int(n_seeds),
+                                             int(seed) & 0xFFFFFFFF, float(amplitude), int(problem_offset),
+                                             _dev(alpha_dev), _dev(waypoints_dev), ctypes.c_void_p(stream)))
+
+    def rank_candidates_dev(self, stats_dev, batch, n_seeds, winner_dev, reports_dev=0, rank_dev=0, stream=0):
+        """Enqueue irm_rank_candidates_dev with raw device addresses (stats: 32-byte irm_stats records; reports:
+        32-byte irm_clearance_report records, 0: none; rank_dev 0: no rank output)."""
+        vp = lambda a: ctypes.c_void_p(int(a) if a else None)  # noqa: E731
+        check(self.lib.irm_rank_candidates_dev(self._h, vp(stats_dev), vp(reports_dev), int(batch), int(n_seeds),
+                                               vp(winner_dev), vp(rank_dev), ctypes.c_void_p(stream)))
+
+    def optimize_multistart_dev(self, batch_dev, n_seeds, winner_dev, workspace_dev, workspace_bytes, seed=0,
+                                amplitude=1.0, problem_offset=0, rank_clearance=False, obstacle_radius_dev=0,
+                                link_radius=0.0, obstacle_velocity_dev=0, goal_xy_dev=0, cand_alpha_dev=0,
+                                cand_traj_dev=0, cand_stats_dev=0, cand_reports_dev=0, rank_dev=0, stream=0):
+        """Enqueue irm_optimize_multistart_dev with raw device addresses: batch_dev (IrmBatchDev of the B problems:
+        alpha0 and series_out 0; its alpha_out / traj_out / stats_out receive the winner's rows), the workspace of
+        multistart_workspace() bytes, winner_dev (B int32) and the optional per-candidate outputs (0: absent)."""
+        ms = IrmMultistart()
+        ms.n_seeds, ms.seed, ms.amplitude = int(n_seeds), int(seed) & 0xFFFFFFFF, float(amplitude)
+        ms.problem_offset, ms.rank_clearance = int(problem_offset), int(bool(rank_clearance))
+        ms.link_radius = float(link_radius)
+        ms.obstacle_radius = int(obstacle_radius_dev) or None
+        out = IrmMultistartOut()
+        out.winner = int(winner_dev) or None
+        out.cand_alpha, out.cand_traj = int(cand_alpha_dev) or None, int(cand_traj_dev) or None
+        out.cand_stats, out.cand_reports = int(cand_stats_dev) or None, int(cand_reports_dev) or None
+        out.rank = int(rank_dev) or None
+        vel = obstacle_velocity_dev or getattr(batch_dev, "obstacle_velocity", 0)
+        check(self.lib.irm_optimize_multistart_dev(self._h, ctypes.byref(ms), ctypes.byref(batch_dev), _dev(vel),
+                                                   _dev(goal_xy_dev), ctypes.byref(out),
+                                                   ctypes.c_void_p(int(workspace_dev) or None), int(workspace_bytes),
+                                                   ctypes.c_void_p(stream)))
 
     def bls_trace_enable(self, cap=256):
         """Record the line-search log of problem 0 of every later BLS optimize (diagnostics)."""

@@ -91,6 +91,10 @@ struct irm_ctx {
     double *d_WT = nullptr, *d_TT = nullptr;
     float* d_kq0 = nullptr;
     int xfer_src = 0;
+    // multi-start seeds (irm_seed_ensemble): the smooth step c of the operator build, and c (N) then the bump φ (N)
+    // on the device (uploaded at first use)
+    std::vector<float> cvec;
+    float* d_cphi = nullptr;
 };
 
 namespace {
@@ -240,6 +244,7 @@ int irm_ctx_create(irm_ctx** out, const irm_params* p) {
         kp.*b.dev = c->d_ops[i];
     }
     if (const char* err = irm::fill_kparams(*p, ops, kp)) return fail(IRM_EINVAL, "%s", err);
+    c->cvec = std::move(ops.cvec);
     c->t = std::move(ops.t);  // kept for irm_kernel_matrices, the eval times and the fit
     if (upload(&c->d_t, c->t)) {
         std::string e = g_err;
@@ -283,6 +288,7 @@ void irm_ctx_destroy(irm_ctx* c) {
     if (c->d_WT) (void)hipFree(c->d_WT);
     if (c->d_TT) (void)hipFree(c->d_TT);
     if (c->d_kq0) (void)hipFree(c->d_kq0);
+    if (c->d_cphi) (void)hipFree(c->d_cphi);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1579,6 +1585,345 @@ int irm_optimize_batch_via(irm_ctx* c, const float* alpha0, const float* start, 
                            const float* goal_xy, const irm_via* via) {
     return optimize_host(c, alpha0, start, goal, obstacles, O, obstacle_stride, B, alpha_out, traj_out, stats_out,
                          series_out, {obstacle_velocity, goal_xy, via});
+}
+
+}  // extern "C"
+
+// ------------------------------------------------- multi-start planning
+namespace {
+
+// c (N) then φ (N) on the device, at first use: φ_n = 16·(p·p), p = t_n·(1 − t_n) in fp32
+int ensure_seed_tables(irm_ctx* c) {
+    if (c->d_cphi) return 0;
+    const int N = c->N;
+    std::vector<float> cphi(2 * (size_t)N);
+    for (int n = 0; n < N; ++n) {
+        const float t = c->t[n];
+        const float om = 1.f - t;
+        const float p = t * om;
+        const float pp = p * p;
+        cphi[n] = c->cvec[n];
+        cphi[(size_t)N + n] = 16.f * pp;
+    }
+    if (upload(&c->d_cphi, cphi)) {
+        if (c->d_cphi) (void)hipFree(c->d_cphi);
+        c->d_cphi = nullptr;
+        return IRM_ENOMEM;
+    }
+    return 0;
+}
+
+// what every seed / multi-start entry point refuses about the ensemble itself
+int check_ensemble(const char* fn, int32_t B, int32_t S, float amplitude, int32_t problem_offset) {
+    if (B < 0) return fail(IRM_EINVAL, "%s: negative batch", fn);
+    if (S < 1 || S > IRM_MAX_SEEDS) return fail(IRM_EINVAL, "%s: n_seeds=%d outside [1, %d]", fn, S, IRM_MAX_SEEDS);
+    if (!(amplitude >= 0.f) || !std::isfinite(amplitude))
+        return fail(IRM_EINVAL, "%s: amplitude=%g must be finite and >= 0", fn, (double)amplitude);
+    if (problem_offset < 0) return fail(IRM_EINVAL, "%s: problem_offset=%d must be >= 0", fn, problem_offset);
+    if ((int64_t)B * S > (int64_t)1 << 24) return fail(IRM_EINVAL, "%s: batch*n_seeds=%lld candidates exceed 2^24", fn, (long long)B * S);
+    return 0;
+}
+
+size_t al256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// The device workspace of irm_optimize_multistart_dev: offsets of its slices (every optional one reserved).
+struct MsLayout {
+    size_t seeds, start, goal, ik, gxy, obs, vel, rad, c_alpha, c_traj, c_stats, c_rep, rank, total;
+};
+
+MsLayout ms_layout(const irm_ctx* c, size_t B, size_t S, size_t stride) {
+    const size_t BS = B * S, nd = (size_t)c->N * c->D, D = (size_t)c->D;
+    MsLayout l{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = off;
+        off += al256(std::max<size_t>(bytes, 4));
+        return o;
+    };
+    l.seeds = take(BS * nd * 4);
+    l.start = take(BS * D * 4);
+    l.goal = take(BS * D * 4);
+    l.ik = take(B * D * 4);
+    l.gxy = take(BS * 8);
+    l.obs = take(BS * stride * 4);
+    l.vel = take(BS * stride * 4);
+    l.rad = take(BS * (stride / 2) * 4);
+    l.c_alpha = take(BS * nd * 4);
+    l.c_traj = take(BS * nd * 4);
+    l.c_stats = take(BS * sizeof(irm_stats));
+    l.c_rep = take(BS * sizeof(irm_clearance_report));
+    l.rank = take(BS * 4);
+    l.total = off;
+    return l;
+}
+
+// what irm_optimize_multistart and its _dev form both refuse (the host form before it stages anything)
+int check_multistart(const char* fn, const irm_ctx* c, const irm_multistart* ms, int32_t B, int32_t O, int32_t stride,
+                     const void* alpha0, const void* series_out, const void* start, const void* goal,
+                     const void* obstacles, const void* goal_xy, const irm_multistart_out* out) {
+    if (!c || !ms || !out || !out->winner || !start) return fail(IRM_EINVAL, "%s: null argument", fn);
+    if (check_ensemble(fn, B, ms->n_seeds, ms->amplitude, ms->problem_offset)) return IRM_EINVAL;
+    if (alpha0) return fail(IRM_EINVAL, "%s: alpha0 must be NULL (the seeds are the call's own)", fn);
+    if (series_out || c->kp.record_series)
+        return fail(IRM_EINVAL, "%s: series_out / record_series: a multi-start call records no series", fn);
+    if (!goal && !goal_xy) return fail(IRM_EINVAL, "%s: goal is NULL without goal_xy", fn);
+    if (check_obs(O) || check_stride(O, stride)) return IRM_EINVAL;
+    if (O > 0 && !obstacles) return fail(IRM_EINVAL, "%s: obstacles pointer missing", fn);
+    if (ms->rank_clearance && c->t_eval.empty())
+        return fail(IRM_EINVAL, "%s: rank_clearance needs an evaluation grid (irm_set_eval_times)", fn);
+    if (!ms->rank_clearance && ms->obstacle_radius)
+        return fail(IRM_EINVAL, "%s: obstacle_radius without rank_clearance", fn);
+    if (!ms->rank_clearance && ms->link_radius != 0.f)
+        return fail(IRM_EINVAL, "%s: link_radius=%g without rank_clearance", fn, (double)ms->link_radius);
+    if (ms->rank_clearance && (!(ms->link_radius >= 0.f) || !std::isfinite(ms->link_radius)))
+        return fail(IRM_EINVAL, "%s: link_radius must be finite and >= 0", fn);
+    if (ms->rank_clearance && ms->obstacle_radius && (stride & 1))
+        return fail(IRM_EINVAL, "%s: obstacle_stride=%d is odd: the radius tables lie obstacle_stride/2 floats apart", fn, stride);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int irm_seed_ensemble_dev(irm_ctx* c, const float* start, const float* goal, int32_t B, int32_t S, uint32_t seed,
+                          float amplitude, int32_t problem_offset, float* alpha, float* waypoints, void* stream) {
+    if (!c || !start || !goal || !alpha) return fail(IRM_EINVAL, "irm_seed_ensemble_dev: null argument");
+    if (check_ensemble("irm_seed_ensemble_dev", B, S, amplitude, problem_offset)) return IRM_EINVAL;
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    int rc = ensure_fit("irm_seed_ensemble_dev", c);
+    if (rc) return rc;
+    if ((rc = ensure_seed_tables(c))) return rc;
+    KParams kp = c->kp;
+    kp.B = B;
+    // the joint range of the clamp: irm_ik_seed's
+    const float lo = (float)((double)c->p.joint_safety_limit * (double)c->p.min_joint_position);
+    const float hi = (float)((double)c->p.joint_safety_limit * (double)c->p.max_joint_position);
+    HIP_TRY(irm::launch_seed_ensemble(kp, c->d_WT, c->d_cphi, start, goal, S, seed, amplitude, (uint32_t)problem_offset,
+                                      lo, hi, alpha, waypoints, (hipStream_t)stream));
+    return IRM_OK;
+}
+
+int irm_seed_ensemble(irm_ctx* c, const float* start, const float* goal, int32_t B, int32_t S, uint32_t seed,
+                      float amplitude, int32_t problem_offset, float* alpha_out, float* waypoints_out) {
+    if (!c || !start || !goal || !alpha_out) return fail(IRM_EINVAL, "irm_seed_ensemble: null argument");
+    if (check_ensemble("irm_seed_ensemble", B, S, amplitude, problem_offset)) return IRM_EINVAL;
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    const size_t sd = (size_t)B * c->D, nd = (size_t)B * S * c->N * c->D;
+    Stage st{c};
+    const size_t o_s = st.take(sd * 4), o_g = st.take(sd * 4), o_a = st.take(nd * 4), o_w = st.take(nd * 4);
+    if (ensure_io(c, st.off)) return IRM_ENOMEM;
+    char* d = st.base();
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d + o_s, start, sd * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d + o_g, goal, sd * 4, hipMemcpyHostToDevice, s));
+    const int rc = irm_seed_ensemble_dev(c, (const float*)(d + o_s), (const float*)(d + o_g), B, S, seed, amplitude,
+                                         problem_offset, (float*)(d + o_a), waypoints_out ? (float*)(d + o_w) : nullptr, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(alpha_out, d + o_a, nd * 4, hipMemcpyDeviceToHost, s));
+    if (waypoints_out) HIP_TRY(hipMemcpyAsync(waypoints_out, d + o_w, nd * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return IRM_OK;
+}
+
+int irm_rank_candidates_dev(irm_ctx* c, const irm_stats* stats, const irm_clearance_report* reports, int32_t B,
+                            int32_t S, int32_t* winner, int32_t* rank, void* stream) {
+    if (!c || !stats || !winner) return fail(IRM_EINVAL, "irm_rank_candidates_dev: null argument");
+    if (check_ensemble("irm_rank_candidates_dev", B, S, 0.f, 0)) return IRM_EINVAL;
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    HIP_TRY(irm::launch_rank_candidates(stats, reports, B, S, winner, rank, (hipStream_t)stream));
+    return IRM_OK;
+}
+
+int irm_rank_candidates(irm_ctx* c, const irm_stats* stats, const irm_clearance_report* reports, int32_t B, int32_t S,
+                        int32_t* winner_out, int32_t* rank_out) {
+    if (!c || !stats || !winner_out) return fail(IRM_EINVAL, "irm_rank_candidates: null argument");
+    if (check_ensemble("irm_rank_candidates", B, S, 0.f, 0)) return IRM_EINVAL;
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    const size_t BS = (size_t)B * S;
+    Stage st{c};
+    const size_t o_st = st.take(BS * sizeof(irm_stats)), o_rp = st.take(BS * sizeof(irm_clearance_report)),
+                 o_w = st.take((size_t)B * 4), o_r = st.take(BS * 4);
+    if (ensure_io(c, st.off)) return IRM_ENOMEM;
+    char* d = st.base();
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d + o_st, stats, BS * sizeof(irm_stats), hipMemcpyHostToDevice, s));
+    if (reports) HIP_TRY(hipMemcpyAsync(d + o_rp, reports, BS * sizeof(irm_clearance_report), hipMemcpyHostToDevice, s));
+    const int rc = irm_rank_candidates_dev(c, (const irm_stats*)(d + o_st),
+                                           reports ? (const irm_clearance_report*)(d + o_rp) : nullptr, B, S,
+                                           (int32_t*)(d + o_w), rank_out ? (int32_t*)(d + o_r) : nullptr, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(winner_out, d + o_w, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    if (rank_out) HIP_TRY(hipMemcpyAsync(rank_out, d + o_r, BS * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return IRM_OK;
+}
+
+int64_t irm_multistart_workspace(const irm_ctx* c, int32_t B, int32_t S, int32_t O, int32_t obstacle_stride) {
+    if (!c) return fail(IRM_EINVAL, "irm_multistart_workspace: null context");
+    if (check_ensemble("irm_multistart_workspace", B, S, 0.f, 0)) return IRM_EINVAL;
+    if (check_obs(O) || check_stride(O, obstacle_stride)) return IRM_EINVAL;
+    return (int64_t)ms_layout(c, (size_t)B, (size_t)S, (size_t)obstacle_stride).total;
+}
+
+int irm_optimize_multistart_dev(irm_ctx* c, const irm_multistart* ms, const irm_batch_dev* a, const float* vel,
+                                const float* gxy, const irm_multistart_out* out, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+    const char* fn = "irm_optimize_multistart_dev";
+    if (!a) return fail(IRM_EINVAL, "%s: null argument", fn);
+    if (check_multistart(fn, c, ms, a->batch, a->n_obstacles, a->obstacle_stride, a->alpha0, a->series_out, a->start,
+                         a->goal, a->obstacles, gxy, out))
+        return IRM_EINVAL;
+    const int B = a->batch, S = ms->n_seeds, O = a->n_obstacles, stride = a->obstacle_stride;
+    const MsLayout l = ms_layout(c, (size_t)B, (size_t)S, (size_t)stride);
+    if (B > 0 && (!workspace || workspace_bytes < (int64_t)l.total))
+        return fail(IRM_EINVAL, "%s: workspace of %lld bytes, irm_multistart_workspace asks for %lld", fn,
+                    (long long)(workspace ? workspace_bytes : 0), (long long)l.total);
+    if (B > 0 && ((uintptr_t)workspace & 255)) return fail(IRM_EINVAL, "%s: workspace is not 256-byte aligned", fn);
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    const int D = c->D, nd = c->N * c->D, BS = B * S;
+    char* w = (char*)workspace;
+    hipStream_t s = (hipStream_t)stream;
+    float* seeds = (float*)(w + l.seeds);
+    float* start_r = (float*)(w + l.start);
+    float* goal_r = (float*)(w + l.goal);
+    if (O == 0) vel = nullptr;  // no obstacle, nothing moves
+    // the goal configuration: given, or the IK seed's for (start, goal_xy)
+    const float* goal = a->goal;
+    if (!goal) {
+        const int rc = irm_ik_seed_dev(c, a->start, gxy, B, (float*)(w + l.ik), nullptr, s);
+        if (rc) return rc;
+        goal = (const float*)(w + l.ik);
+    }
+    int rc = irm_seed_ensemble_dev(c, a->start, goal, B, S, ms->seed, ms->amplitude, ms->problem_offset, seeds, nullptr, s);
+    if (rc) return rc;
+    HIP_TRY(irm::launch_replicate(a->start, start_r, B, S, D, D, s));
+    HIP_TRY(irm::launch_replicate(goal, goal_r, B, S, D, D, s));
+    const float* gxy_r = nullptr;
+    if (gxy) {
+        HIP_TRY(irm::launch_replicate(gxy, (float*)(w + l.gxy), B, S, 2, 2, s));
+        gxy_r = (const float*)(w + l.gxy);
+    }
+    // shared tables (obstacle_stride 0) serve the B·S problems as they are; per-problem ones are replicated
+    const float *obs_r = a->obstacles, *vel_r = vel, *rad_r = ms->rank_clearance && O > 0 ? ms->obstacle_radius : nullptr;
+    if (stride && O > 0) {
+        HIP_TRY(irm::launch_replicate(a->obstacles, (float*)(w + l.obs), B, S, stride, stride, s));
+        obs_r = (const float*)(w + l.obs);
+        if (vel) {
+            HIP_TRY(irm::launch_replicate(vel, (float*)(w + l.vel), B, S, stride, stride, s));
+            vel_r = (const float*)(w + l.vel);
+        }
+        if (rad_r) {
+            HIP_TRY(irm::launch_replicate(rad_r, (float*)(w + l.rad), B, S, stride / 2, stride / 2, s));
+            rad_r = (const float*)(w + l.rad);
+        }
+    }
+    float* c_alpha = out->cand_alpha ? out->cand_alpha : (float*)(w + l.c_alpha);
+    float* c_traj = out->cand_traj ? out->cand_traj : (a->traj_out ? (float*)(w + l.c_traj) : nullptr);
+    irm_stats* c_stats = out->cand_stats ? out->cand_stats : (irm_stats*)(w + l.c_stats);
+    irm_clearance_report* c_rep = out->cand_reports ? out->cand_reports : (irm_clearance_report*)(w + l.c_rep);
+    irm_batch_dev in{};
+    in.alpha0 = seeds;
+    in.start = start_r;
+    in.goal = goal_r;
+    in.obstacles = obs_r;
+    in.n_obstacles = O;
+    in.obstacle_stride = stride;
+    in.batch = BS;
+    in.alpha_out = c_alpha;
+    in.traj_out = c_traj;
+    in.stats_out = c_stats;
+    if ((rc = optimize_dev(c, &in, {vel_r, gxy_r}, stream))) return rc;
+    if (ms->rank_clearance) {
+        rc = irm_clearance_dev(c, c_alpha, obs_r, O, stride, vel_r, rad_r, ms->link_radius, BS, c_rep, nullptr, nullptr,
+                               nullptr, stream);
+        if (rc) return rc;
+    }
+    HIP_TRY(irm::launch_rank_candidates(c_stats, ms->rank_clearance ? c_rep : nullptr, B, S, out->winner, out->rank, s));
+    HIP_TRY(irm::launch_gather_winner(out->winner, B, S, nd, c_alpha, c_traj, c_stats, a->alpha_out, a->traj_out,
+                                      a->stats_out, s));
+    return IRM_OK;
+}
+
+int irm_optimize_multistart(irm_ctx* c, const irm_multistart* ms, const float* alpha0, const float* start,
+                            const float* goal, const float* obstacles, int32_t O, int32_t obstacle_stride, int32_t B,
+                            float* alpha_out, float* traj_out, irm_stats* stats_out, float* series_out,
+                            const float* vel, const float* gxy, const irm_multistart_out* out) {
+    const char* fn = "irm_optimize_multistart";
+    if (check_multistart(fn, c, ms, B, O, obstacle_stride, alpha0, series_out, start, goal, obstacles, gxy, out))
+        return IRM_EINVAL;
+    const size_t nobs = obstacle_stride ? (size_t)B * obstacle_stride : (size_t)O * 2;
+    const size_t nrad = obstacle_stride ? (size_t)B * (obstacle_stride / 2) : (size_t)O;
+    if (O == 0) vel = nullptr;
+    const float* radius = ms->rank_clearance && O > 0 ? ms->obstacle_radius : nullptr;
+    if (vel && check_vel(fn, vel, nobs)) return IRM_EINVAL;
+    if (gxy && check_goal_xy(fn, gxy, (size_t)B)) return IRM_EINVAL;
+    if (radius)
+        for (size_t b = 0; b < (obstacle_stride ? (size_t)B : 1); ++b)
+            for (int o = 0; o < O; ++o) {
+                const float r = radius[b * (size_t)(obstacle_stride / 2) + o];
+                if (!(r >= 0.f) || !std::isfinite(r))
+                    return fail(IRM_EINVAL, "%s: obstacle_radius[%zu] must be finite and >= 0", fn,
+                                b * (size_t)(obstacle_stride / 2) + o);
+            }
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    const int S = ms->n_seeds;
+    const size_t BS = (size_t)B * S, sd = (size_t)B * c->D, nd1 = (size_t)c->N * c->D;
+    const MsLayout l = ms_layout(c, (size_t)B, (size_t)S, (size_t)obstacle_stride);
+    Stage st{c};
+    const size_t o_s = st.take(sd * 4), o_g = st.take(sd * 4), o_o = st.take(std::max<size_t>(nobs, 1) * 4),
+                 o_v = st.take(std::max<size_t>(nobs, 1) * 4), o_p = st.take((size_t)B * 8),
+                 o_rad = st.take(std::max<size_t>(nrad, 1) * 4), o_ao = st.take(B * nd1 * 4), o_to = st.take(B * nd1 * 4),
+                 o_st = st.take((size_t)B * sizeof(irm_stats)), o_win = st.take((size_t)B * 4), o_ws = st.take(l.total);
+    if (ensure_io(c, st.off)) return IRM_ENOMEM;
+    char* d = st.base();
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d + o_s, start, sd * 4, hipMemcpyHostToDevice, s));
+    if (goal) HIP_TRY(hipMemcpyAsync(d + o_g, goal, sd * 4, hipMemcpyHostToDevice, s));
+    if (nobs && O > 0) HIP_TRY(hipMemcpyAsync(d + o_o, obstacles, nobs * 4, hipMemcpyHostToDevice, s));
+    if (vel) HIP_TRY(hipMemcpyAsync(d + o_v, vel, nobs * 4, hipMemcpyHostToDevice, s));
+    if (gxy) HIP_TRY(hipMemcpyAsync(d + o_p, gxy, (size_t)B * 8, hipMemcpyHostToDevice, s));
+    if (radius) HIP_TRY(hipMemcpyAsync(d + o_rad, radius, nrad * 4, hipMemcpyHostToDevice, s));
+    irm_multistart msd = *ms;
+    msd.obstacle_radius = radius ? (const float*)(d + o_rad) : nullptr;
+    irm_batch_dev a{};
+    a.start = (const float*)(d + o_s);
+    a.goal = goal ? (const float*)(d + o_g) : nullptr;
+    a.obstacles = (const float*)(d + o_o);
+    a.n_obstacles = O;
+    a.obstacle_stride = obstacle_stride;
+    a.batch = B;
+    a.alpha_out = (float*)(d + o_ao);
+    a.traj_out = (float*)(d + o_to);
+    a.stats_out = (irm_stats*)(d + o_st);
+    // the candidates' rows stay in the workspace (its own slices) and are copied out from there
+    char* w = d + o_ws;
+    irm_multistart_out od{};
+    od.winner = (int32_t*)(d + o_win);
+    od.cand_traj = out->cand_traj ? (float*)(w + l.c_traj) : nullptr;
+    od.rank = out->rank ? (int32_t*)(w + l.rank) : nullptr;
+    const int rc = irm_optimize_multistart_dev(c, &msd, &a, vel ? (const float*)(d + o_v) : nullptr,
+                                               gxy ? (const float*)(d + o_p) : nullptr, &od, w, (int64_t)l.total, s);
+    if (rc) return rc;
+    if (alpha_out) HIP_TRY(hipMemcpyAsync(alpha_out, d + o_ao, B * nd1 * 4, hipMemcpyDeviceToHost, s));
+    if (traj_out) HIP_TRY(hipMemcpyAsync(traj_out, d + o_to, B * nd1 * 4, hipMemcpyDeviceToHost, s));
+    if (stats_out) HIP_TRY(hipMemcpyAsync(stats_out, d + o_st, (size_t)B * sizeof(irm_stats), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(out->winner, d + o_win, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    if (out->cand_alpha) HIP_TRY(hipMemcpyAsync(out->cand_alpha, w + l.c_alpha, BS * nd1 * 4, hipMemcpyDeviceToHost, s));
+    if (out->cand_traj) HIP_TRY(hipMemcpyAsync(out->cand_traj, w + l.c_traj, BS * nd1 * 4, hipMemcpyDeviceToHost, s));
+    if (out->cand_stats)
+        HIP_TRY(hipMemcpyAsync(out->cand_stats, w + l.c_stats, BS * sizeof(irm_stats), hipMemcpyDeviceToHost, s));
+    if (out->cand_reports && ms->rank_clearance)
+        HIP_TRY(hipMemcpyAsync(out->cand_reports, w + l.c_rep, BS * sizeof(irm_clearance_report), hipMemcpyDeviceToHost, s));
+    if (out->rank) HIP_TRY(hipMemcpyAsync(out->rank, w + l.rank, BS * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return IRM_OK;
 }
 
 }  // extern "C"

@@ -39,5 +39,20 @@ hipError_t launch_clearance(const KParams& p, const float* kqT, int M, const flo
 hipError_t launch_fit_alpha(const KParams& p, const double* wT, const float* traj, float* alpha_out, hipStream_t s);
 hipError_t launch_transfer_alpha(const KParams& p, const double* tT, int n_src, const float* kq0, const float* alpha_src,
                                  float* alpha_out, float* start_out, hipStream_t s);
+// irm_multistart.hip — multi-start planning.  Candidate s of problem b is row b·S + s.
+// Seeds: p.B problems, S candidates each; wT as launch_fit_alpha's; cphi: the smooth step c (N) then the bump φ
+// (N) on the device; start / goal B×D; [lo, hi] the joint range of the clamp; alpha_out B·S×N×D, way_out nullable.
+hipError_t launch_seed_ensemble(const KParams& p, const double* wT, const float* cphi, const float* start,
+                                const float* goal, int S, uint32_t seed, float amplitude, uint32_t problem_offset,
+                                float lo, float hi, float* alpha_out, float* way_out, hipStream_t s);
+// out[(b·S + s)·w + j] = in[b·in_stride + j]
+hipError_t launch_replicate(const float* in, float* out, int B, int S, int w, int in_stride, hipStream_t s);
+// stats B·S, rep B·S (nullable); winner B, rank B·S (nullable)
+hipError_t launch_rank_candidates(const irm_stats* stats, const irm_clearance_report* rep, int B, int S,
+                                  int32_t* winner, int32_t* rank, hipStream_t s);
+// row b·S + winner[b] of cand_* (nd floats per row; one irm_stats) into row b of the outputs (each nullable)
+hipError_t launch_gather_winner(const int32_t* winner, int B, int S, int nd, const float* cand_alpha,
+                                const float* cand_traj, const irm_stats* cand_stats, float* alpha, float* traj,
+                                irm_stats* stats, hipStream_t s);
 
 }  // namespace irm

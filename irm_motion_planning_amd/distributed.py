@@ -15,6 +15,8 @@ the CPU tests) are exactly the four §8e lists:
 
 shard(B, world, rank) gives rank r the rows [lo, hi) of the global batch:
 contiguous, in rank order, the first B mod world ranks one row larger.
+problem_offset(B, world, rank) is lo: a multi-start call of a shard passes it, because a seed depends on
+the problem's global index.
 """
 import os
 
@@ -31,6 +33,12 @@ def shard(B, world, rank):
     base, extra = divmod(int(B), int(world))
     lo = rank * base + min(rank, extra)
     return lo, lo + base + (1 if rank < extra else 0)
+
+
+def problem_offset(B, world, rank):
+    """The global index of a rank's first problem: the problem_offset of its multi-start calls
+    (Context.optimize_multistart), so that every problem gets the seeds it has in the unsharded batch."""
+    return shard(B, world, rank)[0]
 
 
 def _dist():

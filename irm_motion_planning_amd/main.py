@@ -16,7 +16,9 @@ Additive flags (no reference counterpart): --batch-size, --seed,
 interior support rows held to joint or end-effector targets; one stdout line names the chosen rows
 and one reports the via distances), --clearance (the signed clearance between the arm's links and the obstacles as
 discs on M samples: one stdout line, on the batched path a second one and a min_clearance column in the
-summary file) with --obstacle-radius and --link-radius.
+summary file) with --obstacle-radius and --link-radius, and --multi-start (S seeds per problem in one launch, the
+best kept; ranked with the clearance check when --clearance is given; prints the winner and the candidate table)
+with --multi-start-amplitude and --multi-start-seed.
 """
 import argparse
 import os
@@ -167,7 +169,41 @@ def build_parser():
                         help="--clearance: the radius of every obstacle (default: 0 = points)")
     parser.add_argument('--link-radius', type=_radius, default=0.0, metavar='R',
                         help="--clearance: the arm's links as capsules of this radius (default: 0 = segments)")
+    parser.add_argument('--multi-start', type=_seed_count, default=0, metavar='S',
+                        help="Run S seeds per problem in one launch — the straight line plus S-1 smooth random bumps — "
+                             "and keep the best by (constraints fulfilled, collision-free, loss); collisions count when "
+                             "--clearance M is given, with its radii; prints the winner and the candidate table "
+                             "(default: 0 = off)")
+    parser.add_argument('--multi-start-amplitude', type=_radius, default=1.0, metavar='A',
+                        help="--multi-start: the bumps' amplitudes are uniform in [-A, A) per joint (default: 1.0)")
+    parser.add_argument('--multi-start-seed', type=int, default=0, metavar='K',
+                        help="--multi-start: seed of the bumps' hash (default: 0)")
     return parser
+
+
+def _seed_count(x):
+    """--multi-start: 0 (off) or a number of seeds in [1, 64]."""
+    word = str(x).strip()
+    if not word.isdigit() or int(word) > 64:
+        raise argparse.ArgumentTypeError(f"expected a seed count in [0, 64], got {x!r}")
+    return int(word)
+
+
+def multistart_report(info):
+    """--multi-start: the winner and the candidate table of problem 0 (Context.optimize_multistart's info)."""
+    first = np.ndim(info["winner"]) == 0
+    pick = (lambda a: np.asarray(a)) if first else (lambda a: np.asarray(a)[0])  # noqa: E731
+    winner, rank, st = int(pick(info["winner"])), pick(info["rank"]), {k: pick(v) for k, v in info["stats"].items()}
+    ncol = pick(info["reports"]["n_colliding"]) if "reports" in info else None
+    print("multi-start:", info["n_seeds"], "seeds, winner candidate", winner,
+          "(ranked by constraints" + (", collisions" if ncol is not None else "") + ", loss)")
+    for s in range(len(rank)):
+        print("  candidate", s, ": rank", int(rank[s]), ", constraint fulfiled", bool(st["constraints_ok"][s]),
+              *((", colliding samples", int(ncol[s])) if ncol is not None else ()),
+              ", final loss", np.float32(st["final_loss"][s]), ", inner iterations", int(st["inner_iterations"][s]))
+    if not first:
+        w = np.asarray(info["winner"])
+        print("multi-start: the winner is candidate 0 (the plain seed) in", int(np.sum(w == 0)), "of", len(w), "problems")
 
 
 def _radius(x):
@@ -313,7 +349,7 @@ def run_batch(optimizer, args):
                                                goal_xy=xy)
             else:
                 res = optimizer.optimize_batch(start[lo:hi], goal[lo:hi], env.obstacles, series=args.extended_vis,
-                                               goal_xy=xy)
+                                               goal_xy=xy, problem_offset=distributed.problem_offset(B, world, rank))
         et = time.time()
         if world > 1:
             et = st + distributed.reduce_timing(et - st, 0, dev)[0]
@@ -326,6 +362,8 @@ def run_batch(optimizer, args):
         print_stages(optimizer.last_stages)
     alpha, traj, stats = res[:3]
     series = res[3] if args.extended_vis else None
+    if optimizer.multi_start and rank == 0:  # (under torchrun: rank 0's shard)
+        multistart_report(optimizer.last_multistart)
     if world > 1:
         parts = {"alpha": alpha, "traj": traj}
         parts.update({"stat_" + k: np.asarray(v) for k, v in stats.items()})
@@ -432,6 +470,8 @@ def main(argv=None):
         result_alpha = multiple_optimizations()
     if coarse is not None:
         print_stages(optimizer.last_stages)
+    if optimizer.multi_start:
+        multistart_report(optimizer.last_multistart)
     if args.profiling:
         for k, v in optimizer.last_profile.items():
             print("profile", k, v)
