@@ -429,7 +429,7 @@ int irm_optimize_plan_moving(const irm_ctx* ctx, int32_t batch, int32_t n_obstac
  * minimum is min over i of c_i.  Ties go to the lexicographically lowest (i, l, o).  With no obstacles every c_i
  * and the minimum are +INFINITY, every argmin is −1 and nothing collides.  link_out[l] is the minimum of g over
  * the samples and obstacles for link l alone.  The verdict covers the M samples, not the time between them; the
- * links are not checked against each other.
+ * links are not checked against each other here (irm_self_clearance below does that).
  * obstacle_radius: O floats shared by the batch (obstacle_stride 0), else one table per problem at
  * obstacle_stride/2 floats (an odd stride with a radius table is IRM_EINVAL).  obstacle_velocity: as
  * irm_dense_check_moving; NULL and an all-zero table give the same bits.  IRM_EINVAL: no evaluation grid, a
@@ -454,6 +454,52 @@ int irm_clearance_dev(irm_ctx* ctx, const float* alpha_dev, const float* obstacl
                       int32_t obstacle_stride, const float* obstacle_velocity_dev, const float* obstacle_radius_dev,
                       float link_radius, int32_t batch, irm_clearance_report* report_dev, float* clear_dev,
                       float* link_dev, float* joints_dev, void* stream);
+
+/* Self-clearance: the signed distance between the arm's own links on the evaluation times — does the arm touch
+ * itself?  irm_clearance checks the links against obstacles and not against each other; the optimiser's cost sees
+ * points only, so nothing stops a plan that folds the arm through itself.  For trajectory b, evaluation time i of
+ * the context's grid (irm_set_eval_times) and the link pairs (a, b) with 0 ≤ a, a + 2 ≤ b ≤ D − 1 — adjacent links
+ * share a joint and are never a pair — in lexicographic order (0,2), (0,3), …, (D−3, D−1), P = (D−1)(D−2)/2 of
+ * them, everything in fp32 and in this order:
+ *   q, c_l, τ_l, sn, cs, p_l   irm_clearance's, bit for bit (one shared prefix in the kernels), p_{−1} = (0, 0)
+ *   e_l, w_l   = (L_l·cs_l, L_l·sn_l), 1/(L_l·L_l)              irm_clearance's link direction and inverse squared length
+ *   segment l  from A = p_{l−1} to p_l with direction e_l; the far end point is the stored joint position p_l, not A + e
+ *   dist(x; A, e, w):  u = x − A                                  per coordinate
+ *                      s = min(max(fmaf(u_y, e_y, u_x·e_x)·w, 0), 1)
+ *                      r = (fmaf(−s, e_x, u_x), fmaf(−s, e_y, u_y))
+ *                      d = sqrt(fmaf(r_y, r_y, r_x·r_x))          the IEEE (correctly rounded) square root
+ *   orient(x; A, e) = fmaf(u_x, e_y, −(u_y·e_x)),  u = x − A     which side of the link's line x lies on
+ *   d1, o1     = dist, orient(p_{b−1}; link a)      d2, o2 = dist, orient(p_b; link a)
+ *   d3, o3     = dist, orient(p_{a−1}; link b)      d4, o4 = dist, orient(p_a; link b)
+ *   crossing   o1 and o2 have strictly opposite signs and o3 and o4 have strictly opposite signs: the signs are
+ *              compared, not a product (which can underflow to 0 or lose its sign), and a zero is not a sign — the
+ *              end-point distances cover touching and collinear overlap
+ *   d          = 0 if the pair crosses, else min(d1, d2, d3, d4)
+ *   g          = d − 2·link_radius                                the signed clearance of two capsules
+ * The pair collides iff it crosses or g < 0 (g = 0 without a crossing, touching, does not — irm_clearance's
+ * convention; with link_radius = 0 a collision is exactly a crossing).  Sample i has c_i = min over the pairs of g
+ * and collides iff one of its pairs does; the report's minimum is min over i of c_i.  Ties go to the
+ * lexicographically lowest (i, a, b).  With P = 0 (D ≤ 2) every c_i and the minimum are +INFINITY, every argmin is
+ * −1 and nothing collides.  pair_out[p] is the minimum of g over the samples for pair p alone, in the pair order.
+ * The verdict covers the M samples, not the time between them; one radius for the whole arm; the base is no body.
+ * IRM_EINVAL: no evaluation grid, a negative batch, a negative or non-finite link_radius, a NULL alpha or report.
+ * batch = 0 is a no-op.  A problem's result does not depend on the rest of the batch.
+ * Additive symbols: IRM_ABI_VERSION stays 3 and no struct changes layout; no reference counterpart. */
+typedef struct irm_self_clearance_report {
+    float min_clearance;
+    int32_t argmin_time, argmin_link_a, argmin_link_b; /* indices into t_eval and the links (a + 2 ≤ b); -1 if D ≤ 2 */
+    int32_t n_colliding, first_colliding;              /* samples with a colliding pair; first index into t_eval or -1 */
+    int32_t collision_free;                            /* n_colliding == 0 */
+    int32_t n_crossing;                                /* samples where some pair crosses */
+} irm_self_clearance_report;
+/* report_out: B records.  clear_out B×M (c_i), pair_out B×P, joints_out B×M×D×2 (x_l, y_l of every sample: the bits
+ * of irm_clearance's joints_out for the same α and grid): each nullable. */
+int irm_self_clearance(irm_ctx* ctx, const float* alpha, float link_radius, int32_t batch,
+                       irm_self_clearance_report* report_out, float* clear_out, float* pair_out, float* joints_out);
+/* Same, device pointers, enqueue-only on `stream` (hipStream_t); allocates nothing. */
+int irm_self_clearance_dev(irm_ctx* ctx, const float* alpha_dev, float link_radius, int32_t batch,
+                           irm_self_clearance_report* report_dev, float* clear_dev, float* pair_dev, float* joints_dev,
+                           void* stream);
 
 /* End-effector goals: plan to a Cartesian target.  A problem may carry goal_xy = (p_x, p_y); row N−1 of the
  * trajectory is then held to the target through the end-effector FK f (robot.py:29-36) and its 2×D Jacobian

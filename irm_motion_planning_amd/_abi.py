@@ -183,6 +183,8 @@ _DENSE = [_h, c_float_p, c_float_p, _i32, _i32, _i32, ctypes.POINTER(IrmDenseRep
 _PLAN = [_h, _i32, _i32, _i32, ctypes.POINTER(IrmLaunchPlan)]
 _CLEARANCE = [_h, c_float_p, c_float_p, _i32, _i32, c_float_p, c_float_p, _f, _i32,
               ctypes.POINTER(_clearance.IrmClearanceReport), c_float_p, c_float_p, c_float_p]
+_SELF_CLEARANCE = [_h, c_float_p, _f, _i32, ctypes.POINTER(_clearance.IrmSelfClearanceReport), c_float_p, c_float_p,
+                   c_float_p]
 
 # name -> (restype, argtypes); every symbol include/irm.h declares.
 PROTOTYPES = {
@@ -229,6 +231,9 @@ PROTOTYPES = {
     # clearance of the links against disc obstacles (velocity and radius tables nullable)
     "irm_clearance": (ctypes.c_int, _CLEARANCE),
     "irm_clearance_dev": (ctypes.c_int, _CLEARANCE + [_h]),
+    # clearance of the links against each other
+    "irm_self_clearance": (ctypes.c_int, _SELF_CLEARANCE),
+    "irm_self_clearance_dev": (ctypes.c_int, _SELF_CLEARANCE + [_h]),
     "irm_ik_seed": (ctypes.c_int, [_h, c_float_p, c_float_p, _i32, c_float_p, c_float_p]),
     "irm_ik_seed_dev": (ctypes.c_int, [_h, c_float_p, c_float_p, _i32, c_float_p, c_float_p, _h]),
     # multi-start planning: seed ensembles, ranking, and the call (descriptor, irm_optimize_batch_task's arguments,

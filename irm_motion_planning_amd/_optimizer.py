@@ -66,6 +66,8 @@ class _PersistentOptimizer:
                 raise ValueError("--multi-start does not combine with via-points, --extended-vis or --coarse-n-timesteps")
             if getattr(args, "clearance", 0) > 0:
                 self.context.set_eval_times(np.linspace(0, 1, args.clearance, dtype=np.float32))
+            elif getattr(args, "self_clearance", 0) > 0:  # (both checks rank on one grid: --clearance's when given)
+                self.context.set_eval_times(np.linspace(0, 1, args.self_clearance, dtype=np.float32))
         self.last_stats = None
         self.last_profile = {}
         t1 = time.time()
@@ -79,11 +81,15 @@ class _PersistentOptimizer:
         candidate table."""
         a = self.args
         ranked = getattr(a, "clearance", 0) > 0
+        ranked_self = getattr(a, "self_clearance", 0) > 0
+        if ranked_self:  # (the reports after the run set their own grids)
+            self.context.set_eval_times(np.linspace(0, 1, a.clearance if ranked else a.self_clearance, dtype=np.float32))
         alpha, traj, stats, info = self.context.optimize_multistart(
             start, goal, obstacles, self.multi_start, seed=getattr(a, "multi_start_seed", 0),
             amplitude=getattr(a, "multi_start_amplitude", 1.0), problem_offset=problem_offset, rank_clearance=ranked,
-            obstacle_radius=a.obstacle_radius if ranked else None, link_radius=a.link_radius if ranked else 0.0,
-            obstacle_velocity=vel, goal_xy=goal_xy, candidates=True)
+            obstacle_radius=a.obstacle_radius if ranked else None,
+            link_radius=a.link_radius if ranked or ranked_self else 0.0,
+            obstacle_velocity=vel, goal_xy=goal_xy, candidates=True, rank_self_clearance=ranked_self)
         self.last_multistart = info
         return alpha, traj, stats
 

@@ -14,7 +14,8 @@ start/goal — so every reference visualisation script reads them unchanged, and
   trajectory_series_batch.npz   series (B × S × N × D), series_len (B)  with --extended-vis
   trajectory_batch_summary.txt  per problem: avg cost, max cost, constraint flag,
                                 inner / outer iterations, gradient evaluations (and, with
-                                --clearance, the minimum clearance as a last column)
+                                --clearance, the minimum clearance as a last column; with --self-clearance,
+                                the minimum self-clearance after it)
 """
 import numpy as np
 
@@ -75,8 +76,9 @@ def read_series_batch(path):
     return [ser[b, : int(ln[b])] for b in range(ser.shape[0])]
 
 
-def write_summary(path, avg, mx, ok, stats, min_clearance=None):
-    """min_clearance (--clearance): one more column; without it the file is what it always was."""
+def write_summary(path, avg, mx, ok, stats, min_clearance=None, min_self_clearance=None):
+    """min_clearance (--clearance), min_self_clearance (--self-clearance): one more column each; without them the file
+    is what it always was."""
     cols = [np.asarray(avg, np.float64), np.asarray(mx, np.float64), np.asarray(ok, np.int64),
             np.asarray(stats["inner_iterations"]), np.asarray(stats["outer_iterations"]),
             np.asarray(stats["grad_evals"])]
@@ -85,5 +87,9 @@ def write_summary(path, avg, mx, ok, stats, min_clearance=None):
         cols.append(np.asarray(min_clearance, np.float64))
         fmt.append("%.9g")
         names.append("min_clearance")
+    if min_self_clearance is not None:
+        cols.append(np.asarray(min_self_clearance, np.float64))
+        fmt.append("%.9g")
+        names.append("min_self_clearance")
     table = np.stack([np.asarray(c, np.float64) for c in cols], axis=1)
     np.savetxt(path, table, fmt=fmt, header=" ".join(names))

@@ -8,8 +8,9 @@ irm_launch.hpp, the launchers, and the part headers irm_wave / irm_prof / irm_ph
 irm_opt_common / irm_dispatch / irm_launch_decl .hpp) are
 instantiated in one object per problem shape (csrc/irm_opt_inst.hip compiled
 with IRM_INST_*), so the objects build in parallel; the host-API kernels and dispatch
-(irm_kernels.hip), the kernels of their own units (irm_dense.hip, irm_clearance.hip, irm_fit.hip, irm_multistart.hip;
-irm_dense_sample.hpp is what the first two share, irm_fit_apply.hpp the last two), the C ABI (irm_host.cpp) and the device-free operator build
+(irm_kernels.hip), the kernels of their own units (irm_dense.hip, irm_clearance.hip, irm_self_clearance.hip,
+irm_fit.hip, irm_multistart.hip; irm_dense_sample.hpp is what the first three share, irm_fk_prefix.hpp the two
+clearance units, irm_fit_apply.hpp the last two), the C ABI (irm_host.cpp) and the device-free operator build
 behind irm_ctx_create (irm_operator.cpp: build_operators, fill_kparams,
 choose_shape; no HIP header) are the other objects.  irm_layout.hpp is what
 host and kernels share without a HIP type (KParams, fragment and LDS layouts),
@@ -123,6 +124,8 @@ def _units():
     u += [("irm_dense", "irm_dense.hip", [])]
     # link-against-disc clearance on the evaluation times (irm_clearance): a kernel and launcher of its own
     u += [("irm_clearance", "irm_clearance.hip", [])]
+    # link-against-link clearance on the evaluation times (irm_self_clearance): a kernel and launcher of its own
+    u += [("irm_self_clearance", "irm_self_clearance.hip", [])]
     # fitting and re-timing (irm_fit_alpha, irm_transfer_alpha): kernels and launchers of their own
     u += [("irm_fit", "irm_fit.hip", [])]
     # multi-start planning (irm_seed_ensemble, irm_rank_candidates, irm_optimize_multistart): seeds, replicate, rank, gather

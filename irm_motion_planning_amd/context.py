@@ -11,7 +11,8 @@ import numpy as np
 
 from . import _abi
 from ._abi import IrmBatchDev, IrmDenseReport, IrmInfo, IrmLaunchPlan, IrmParams, IrmStats, check, load_library
-from .clearance import CLEARANCE_REPORT_FIELDS, IrmClearanceReport
+from .clearance import (CLEARANCE_REPORT_FIELDS, SELF_CLEARANCE_REPORT_FIELDS, IrmClearanceReport,
+                        IrmSelfClearanceReport, self_pairs)
 from .multistart import IRM_MAX_SEEDS, IrmMultistart, IrmMultistartOut
 from .via import IrmVia, ViaPoints
 
@@ -302,6 +303,28 @@ class Context:
                 out[name] = arr[0] if single else arr
         return out
 
+    def self_clearance(self, alpha, link_radius=0.0, with_samples=False, with_pairs=False, with_joints=False):
+        """Signed clearance between the arm's own links (every pair (a, b), a + 2 ≤ b, each link a capsule of
+        link_radius) on the evaluation times (irm_self_clearance): a dict of arrays named as
+        irm_self_clearance_report's fields, plus `clearance` ((B×)M: every sample's minimum), `pair_clearance`
+        ((B×)P: every pair's own minimum, in the order of clearance.self_pairs) and `joints` ((B×)M×D×2: the joint
+        positions of every sample, the bits of clearance()'s) on request."""
+        a, single = self._batch(alpha, (self.N, self.D))
+        B = a.shape[0]
+        M = max(int(self.lib.irm_eval_times(self._h, None)), 0)
+        rep = (IrmSelfClearanceReport * max(B, 1))()
+        clear = np.zeros((B, M), np.float32) if with_samples else None
+        pair = np.zeros((B, len(self_pairs(self.D))), np.float32) if with_pairs else None
+        joints = np.zeros((B, M, self.D, 2), np.float32) if with_joints else None
+        check(self.lib.irm_self_clearance(self._h, _ptr(a), float(link_radius), B, rep, _ptr(clear), _ptr(pair),
+                                          _ptr(joints)))
+        out = _report(rep, SELF_CLEARANCE_REPORT_FIELDS, ("collision_free",), False)
+        out = {k: (v[0] if single else v[:B]) for k, v in out.items()}
+        for name, arr in (("clearance", clear), ("pair_clearance", pair), ("joints", joints)):
+            if arr is not None:
+                out[name] = arr[0] if single else arr
+        return out
+
     # ------------------------------------------------- fitting and re-timing
     def set_fit_ridge(self, ridge):
         """The ridge ρ of every later fit_alpha / transfer_alpha (irm_set_fit_ridge: rebuilds W = (K + ρI)⁻¹ and
@@ -357,6 +380,14 @@ class Context:
                                          int(obstacle_stride), _dev(obstacle_velocity_dev), _dev(obstacle_radius_dev),
                                          float(link_radius), int(batch), rep, _dev(clear_dev), _dev(link_dev),
                                          _dev(joints_dev), ctypes.c_void_p(stream)))
+
+    def self_clearance_dev(self, alpha_dev, batch, report_dev, link_radius=0.0, clear_dev=0, pair_dev=0, joints_dev=0,
+                           stream=0):
+        """Enqueue irm_self_clearance_dev with raw device addresses (e.g. torch data_ptr()); 0: that output is
+        absent.  report_dev: batch records of 32 bytes (irm_self_clearance_report)."""
+        rep = ctypes.cast(ctypes.c_void_p(int(report_dev) if report_dev else None), ctypes.POINTER(IrmSelfClearanceReport))
+        check(self.lib.irm_self_clearance_dev(self._h, _dev(alpha_dev), float(link_radius), int(batch), rep,
+                                              _dev(clear_dev), _dev(pair_dev), _dev(joints_dev), ctypes.c_void_p(stream)))
 
     def ik_seed_dev(self, start_dev, goal_xy_dev, batch, q_dev, residual_dev=0, stream=0):
         """Enqueue irm_ik_seed_dev with raw device addresses; residual_dev 0: no residual output."""
@@ -663,7 +694,7 @@ class Context:
 
     def optimize_multistart(self, start, goal, obstacles, n_seeds, seed=0, amplitude=1.0, problem_offset=0,
                             rank_clearance=False, obstacle_radius=None, link_radius=0.0, obstacle_velocity=None,
-                            goal_xy=None, candidates=False, via=None, series=False):
+                            goal_xy=None, candidates=False, via=None, series=False, rank_self_clearance=False):
         """optimize() from S seeds per problem, ranked and gathered on the device (irm_optimize_multistart): the
         seeds of seed_ensemble, the plain optimiser launch on the B·S replicated problems, with rank_clearance the
         clearance check of every candidate on the evaluation times (set_eval_times; obstacle_radius / link_radius
@@ -672,9 +703,16 @@ class Context:
         (B,) and, with candidates=True, info["alpha"], info["traj"] (B, S, N, D), info["stats"] (a dict of (B, S)
         arrays), info["rank"] (B, S) and with rank_clearance info["reports"] (a dict of (B, S) arrays).
         goal=None with goal_xy: the goal configuration is ik_seed(start, goal_xy), as in optimize().  Via-points and
-        series recording have no multi-start form (IrmError)."""
+        series recording have no multi-start form (IrmError).
+        rank_self_clearance: also run self_clearance (link_radius) on every candidate, add its n_colliding to the
+        obstacle check's counts (to zeros without rank_clearance), rank again with rank_candidates and return the
+        new winner's rows from the candidate tables — host glue over the device calls; info["self_reports"] (a
+        dict of (B, S) arrays) is added and info["rank"] is always present."""
         if self._has_via(via):
             raise _abi.IrmError("irm error -22: via: via-points have no multi-start form (the via seed is a path of its own)")
+        if rank_self_clearance:
+            return self._multistart_self(start, goal, obstacles, n_seeds, seed, amplitude, problem_offset, rank_clearance,
+                                         obstacle_radius, link_radius, obstacle_velocity, goal_xy, candidates, series)
         s, single = self._batch(start, (self.D,))
         B, S = s.shape[0], int(n_seeds)
         gxy = None if goal_xy is None else self._goal_xy(goal_xy, B)
@@ -723,6 +761,42 @@ class Context:
             if rank_clearance:
                 rep = _report(c_rep, CLEARANCE_REPORT_FIELDS, ("collision_free",), False)
                 info["reports"] = {k: v[:rows].reshape(shape) for k, v in rep.items()}
+        if single:
+            alpha, traj = alpha[0], traj[0]
+            st = {k: v[0] for k, v in st.items()}
+            info = {k: (v[0] if isinstance(v, np.ndarray) else {n: a[0] for n, a in v.items()} if isinstance(v, dict) else v)
+                    for k, v in info.items()}
+        return alpha, traj, st, info
+
+    def _multistart_self(self, start, goal, obstacles, n_seeds, seed, amplitude, problem_offset, rank_clearance,
+                         obstacle_radius, link_radius, obstacle_velocity, goal_xy, candidates, series):
+        """optimize_multistart(rank_self_clearance=True): the device call with its candidate tables, the
+        self-clearance check of the B·S candidate α, the ranking on the summed collision counts and the winner's
+        rows."""
+        if int(self.lib.irm_eval_times(self._h, None)) <= 0:
+            raise _abi.IrmError("irm error -22: optimize_multistart: rank_self_clearance needs an evaluation grid "
+                                "(set_eval_times)")
+        if not (np.isfinite(link_radius) and link_radius >= 0):
+            raise _abi.IrmError("irm error -22: optimize_multistart: link_radius must be finite and >= 0")
+        s, single = self._batch(start, (self.D,))
+        B = s.shape[0]
+        _, _, _, info = self.optimize_multistart(
+            s, goal, obstacles, n_seeds, seed=seed, amplitude=amplitude, problem_offset=problem_offset,
+            rank_clearance=rank_clearance, obstacle_radius=obstacle_radius if rank_clearance else None,
+            link_radius=link_radius if rank_clearance else 0.0, obstacle_velocity=obstacle_velocity, goal_xy=goal_xy,
+            candidates=True, series=series)
+        S = info["alpha"].shape[1]
+        rep = self.self_clearance(info["alpha"].reshape(B * S, self.N, self.D), link_radius=link_radius)
+        info["self_reports"] = {k: np.asarray(v).reshape(B, S) for k, v in rep.items()}
+        ncol = info["self_reports"]["n_colliding"].astype(np.int64)
+        if rank_clearance:
+            ncol = ncol + info["reports"]["n_colliding"]
+        info["winner"], info["rank"] = self.rank_candidates(info["stats"], ncol, n_seeds=S)
+        rows = np.arange(B)
+        alpha, traj = info["alpha"][rows, info["winner"]].copy(), info["traj"][rows, info["winner"]].copy()
+        st = {k: v[rows, info["winner"]].copy() for k, v in info["stats"].items()}
+        if not candidates:
+            info = {k: v for k, v in info.items() if k in ("winner", "n_seeds", "rank", "self_reports")}
         if single:
             alpha, traj = alpha[0], traj[0]
             st = {k: v[0] for k, v in st.items()}

@@ -10,7 +10,8 @@
 // the link's two components, the links and then the samples combine with "lower value, then lower index".
 #include "irm_dense_sample.hpp"  // kDenseT, dense_sample, dense_stage_alpha
 #include "irm_dispatch.hpp"
-#include "irm_physics.hpp"  // sincos_fast, sincos_poly, stage_obstacles
+#include "irm_fk_prefix.hpp"  // fk_prefix
+#include "irm_physics.hpp"    // stage_obstacles
 #include "irm_wave.hpp"     // wred_*, amax_step
 
 namespace irm {
@@ -67,46 +68,9 @@ __global__ __launch_bounds__(kDenseT) void k_clearance(KParams P, const float* k
         const int ii = live ? i : M - 1;
         float q[D], v[D];
         dense_sample<D, false>(P, Al, kqT, nullptr, (unsigned)M, (unsigned)ii, q, v);
-        // FK prefix: c_l, sincos_fast's values (the wave-uniform choice eval_waypoint makes), fmaf-accumulated joints,
-        // with the rounding of every prefix addition kept (two-sum): c_l + tail_l is the angle sum to second order
-        float cum[D], tail[D], sn[D], cs[D], px[D], py[D];
-        bool big = false;
-#pragma unroll
-        for (int l = 0; l < D; ++l) {
-            if (l == 0) {
-                cum[0] = q[0];
-                tail[0] = 0.f;
-            } else {
-                const float s = cum[l - 1] + q[l];
-                const float bb = s - cum[l - 1];
-                const float err = (cum[l - 1] - (s - bb)) + (q[l] - bb);  // exactly (c_{l−1} + q_l) − s
-                cum[l] = s;
-                tail[l] = tail[l - 1] + err;
-            }
-            big |= fabsf(cum[l]) > 1.0e4f;
-        }
-        if (__builtin_expect(__ballot(big) != 0ull, 0)) {
-#pragma unroll
-            for (int l = 0; l < D; ++l) sincos_fast(cum[l], sn[l], cs[l]);
-        } else {
-#pragma unroll
-            for (int l = 0; l < D; ++l) sincos_poly(cum[l], sn[l], cs[l]);
-        }
-        // sin / cos of c_l + tail_l to first order in the tail (|tail| ≲ 1e-6: the second order is below 1e-12)
-#pragma unroll
-        for (int l = 0; l < D; ++l) {
-            const float s0 = sn[l], c0 = cs[l];
-            sn[l] = fmaf(tail[l], c0, s0);
-            cs[l] = fmaf(-tail[l], s0, c0);
-        }
-        float fx = 0.f, fy = 0.f;
-#pragma unroll
-        for (int l = 0; l < D; ++l) {
-            fx = fmaf(P.link[l], cs[l], fx);
-            fy = fmaf(P.link[l], sn[l], fy);
-            px[l] = fx;
-            py[l] = fy;
-        }
+        // FK prefix (irm_fk_prefix.hpp): sines, cosines and the fmaf-accumulated joints of c_l + tail_l
+        float sn[D], cs[D], px[D], py[D];
+        fk_prefix<D>(P, q, sn, cs, px, py);
         if (A.joints && live) {
             float* jo = A.joints + ((size_t)b * M + i) * (2 * D);
 #pragma unroll

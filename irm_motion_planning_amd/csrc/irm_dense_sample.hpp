@@ -1,7 +1,7 @@
 // irm_dense_sample.hpp — what the kernels that evaluate a trajectory at the context's evaluation times share:
 // the workgroup shape, the staging of a problem's α into LDS and one lane's sample q(t_eval[i]), v(t_eval[i]) in
-// irm_eval_any's arithmetic.  Included by irm_dense.hip (k_eval_any, k_dense_check) and irm_clearance.hip
-// (k_clearance).
+// irm_eval_any's arithmetic.  Included by irm_dense.hip (k_eval_any, k_dense_check), irm_clearance.hip
+// (k_clearance) and irm_self_clearance.hip (k_self_clearance).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,7 +1,7 @@
 // irm_dispatch.hpp — host-side launch helpers: run-time D and workgroup size to a template argument
 // (dispatch_d, dispatch_t) and a launch with its dynamic LDS request (launch_lds).  Host code only.
-// Included by every unit that launches a kernel: irm_kernels.hip, irm_dense.hip, irm_clearance.hip, irm_fit.hip,
-// irm_kernels_impl.hpp.
+// Included by every unit that launches a kernel: irm_kernels.hip, irm_dense.hip, irm_clearance.hip,
+// irm_self_clearance.hip, irm_fit.hip, irm_kernels_impl.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 

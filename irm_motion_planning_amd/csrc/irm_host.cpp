@@ -1183,6 +1183,70 @@ int irm_clearance(irm_ctx* c, const float* alpha, const float* obstacles, int32_
     return IRM_OK;
 }
 
+// ------------------------------------------------- clearance of the links against each other
+}  // extern "C"
+
+namespace {
+
+// what irm_self_clearance and irm_self_clearance_dev both refuse (fn: the entry point's name)
+int self_clearance_check(const char* fn, const irm_ctx* c, const float* alpha, float link_radius, int32_t B,
+                         const void* report) {
+    if (!c) return fail(IRM_EINVAL, "%s: null argument: ctx", fn);
+    if (c->t_eval.empty()) return fail(IRM_EINVAL, "%s: no evaluation times set (irm_set_eval_times)", fn);
+    if (B < 0) return fail(IRM_EINVAL, "%s: negative batch", fn);
+    if (!(link_radius >= 0.f) || !std::isfinite(link_radius))
+        return fail(IRM_EINVAL, "%s: link_radius must be finite and >= 0", fn);
+    if (B > 0 && !alpha) return fail(IRM_EINVAL, "%s: null argument: alpha", fn);
+    if (B > 0 && !report) return fail(IRM_EINVAL, "%s: null argument: report", fn);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int irm_self_clearance_dev(irm_ctx* c, const float* alpha, float link_radius, int32_t B,
+                           irm_self_clearance_report* report, float* clear, float* pair, float* joints, void* stream) {
+    if (self_clearance_check("irm_self_clearance_dev", c, alpha, link_radius, B, report)) return IRM_EINVAL;
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    KParams kp = c->kp;
+    kp.B = B;
+    kp.alpha0 = alpha;
+    HIP_TRY(irm::launch_self_clearance(kp, c->d_KqT, (int)c->t_eval.size(), link_radius, report, clear, pair, joints,
+                                       (hipStream_t)stream));
+    return IRM_OK;
+}
+
+int irm_self_clearance(irm_ctx* c, const float* alpha, float link_radius, int32_t B,
+                       irm_self_clearance_report* report_out, float* clear_out, float* pair_out, float* joints_out) {
+    if (self_clearance_check("irm_self_clearance", c, alpha, link_radius, B, report_out)) return IRM_EINVAL;
+    if (set_device(c)) return IRM_EDEVICE;
+    if (B == 0) return IRM_OK;
+    const int N = c->N, D = c->D, M = (int)c->t_eval.size();
+    const size_t np = D > 2 ? (size_t)(D - 1) * (D - 2) / 2 : 0;
+    const size_t nd = (size_t)B * N * D, bm = (size_t)B * M, bp = (size_t)B * np;
+    Stage st{c};
+    const size_t o_a = st.take(nd * 4), o_r = st.take((size_t)B * sizeof(irm_self_clearance_report)),
+                 o_c = st.take(bm * 4), o_p = st.take(std::max<size_t>(bp, 1) * 4),
+                 o_j = st.take(joints_out ? bm * D * 2 * 4 : 4);
+    if (ensure_io(c, st.off)) return IRM_ENOMEM;
+    char* d = st.base();
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d + o_a, alpha, nd * 4, hipMemcpyHostToDevice, s));
+    const int rc = irm_self_clearance_dev(c, (const float*)(d + o_a), link_radius, B,
+                                          (irm_self_clearance_report*)(d + o_r), clear_out ? (float*)(d + o_c) : nullptr,
+                                          pair_out ? (float*)(d + o_p) : nullptr,
+                                          joints_out ? (float*)(d + o_j) : nullptr, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(report_out, d + o_r, (size_t)B * sizeof(irm_self_clearance_report), hipMemcpyDeviceToHost, s));
+    if (clear_out) HIP_TRY(hipMemcpyAsync(clear_out, d + o_c, bm * 4, hipMemcpyDeviceToHost, s));
+    if (pair_out && bp) HIP_TRY(hipMemcpyAsync(pair_out, d + o_p, bp * 4, hipMemcpyDeviceToHost, s));
+    if (joints_out) HIP_TRY(hipMemcpyAsync(joints_out, d + o_j, bm * D * 2 * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return IRM_OK;
+}
+
 // ------------------------------------------------- fitting and re-timing
 }  // extern "C"
 

@@ -33,6 +33,11 @@ hipError_t launch_dense_check(const KParams& p, const float* kqT, const float* d
 hipError_t launch_clearance(const KParams& p, const float* kqT, int M, const float* radius, int radius_stride,
                             float link_radius, irm_clearance_report* rep, float* clear, float* link, float* joints,
                             hipStream_t s);
+// irm_self_clearance.hip — link-against-link clearance on the evaluation times (irm_self_clearance).  α from
+// p.alpha0; rep B, clear B×M, pair B×(D−1)(D−2)/2, joints B×M×D×2 (the last three nullable).
+hipError_t launch_self_clearance(const KParams& p, const float* kqT, int M, float link_radius,
+                                 irm_self_clearance_report* rep, float* clear, float* pair, float* joints,
+                                 hipStream_t s);
 // irm_fit.hip — fitting and re-timing.  wT / tT: the fit / transfer operator on the device in fp64, transposed
 // ([source row m][waypoint n], n_src × N; W is N × N); kq0: the fp32 query row of the source grid at t0 (n_src);
 // p.B problems of p.N waypoints.  start_out nullable.

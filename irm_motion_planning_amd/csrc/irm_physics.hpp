@@ -1,8 +1,8 @@
 // irm_physics.hpp — what one lane computes for one waypoint: sin/cos, FK, the obstacle potential, the
 // end-effector and via rows, the joint-limit penalties, their gradients, the evaluation's reductions and the
 // staging of obstacles and α into LDS.  Included by irm_kernels_impl.hpp (every optimiser kernel), by
-// irm_dense.hip (eval_waypoint_rt, stage_obstacles), by irm_clearance.hip (sincos_fast / sincos_poly, stage_obstacles)
-// and by irm_kernels.hip (sincos_fast).
+// irm_dense.hip (eval_waypoint_rt, stage_obstacles), by irm_clearance.hip (stage_obstacles), by irm_fk_prefix.hpp
+// (sincos_fast / sincos_poly: the clearance kernels' FK) and by irm_kernels.hip (sincos_fast).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

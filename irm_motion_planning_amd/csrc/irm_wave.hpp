@@ -1,6 +1,7 @@
 // irm_wave.hpp — wave-level device helpers of the gfx950 kernels: the packed-fp32 types, the DPP wave
 // reductions (sum, max, min, argmax with first-index ties) and the store of a 16x16 MFMA result tile.
-// Included by irm_physics.hpp, irm_opt_common.hpp, irm_kernels_impl.hpp, irm_dense.hip and irm_clearance.hip.
+// Included by irm_physics.hpp, irm_opt_common.hpp, irm_kernels_impl.hpp, irm_dense.hip, irm_clearance.hip and
+// irm_self_clearance.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

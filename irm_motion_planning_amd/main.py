@@ -16,8 +16,10 @@ Additive flags (no reference counterpart): --batch-size, --seed,
 interior support rows held to joint or end-effector targets; one stdout line names the chosen rows
 and one reports the via distances), --clearance (the signed clearance between the arm's links and the obstacles as
 discs on M samples: one stdout line, on the batched path a second one and a min_clearance column in the
-summary file) with --obstacle-radius and --link-radius, and --multi-start (S seeds per problem in one launch, the
-best kept; ranked with the clearance check when --clearance is given; prints the winner and the candidate table)
+summary file) with --obstacle-radius and --link-radius, --self-clearance (the same for the arm's links against each
+other: one stdout line, on the batched path a second one and a min_self_clearance column), and --multi-start (S seeds per problem in one launch, the
+best kept; ranked with the clearance check when --clearance is given, and with the self-clearance check when
+--self-clearance is; prints the winner and the candidate table)
 with --multi-start-amplitude and --multi-start-seed.
 """
 import argparse
@@ -169,6 +171,12 @@ def build_parser():
                         help="--clearance: the radius of every obstacle (default: 0 = points)")
     parser.add_argument('--link-radius', type=_radius, default=0.0, metavar='R',
                         help="--clearance: the arm's links as capsules of this radius (default: 0 = segments)")
+    parser.add_argument('--self-clearance', type=_sample_count, default=0, metavar='M',
+                        help="After the report (and --clearance), evaluate the result on linspace(0, 1, M) and print the "
+                             "smallest signed distance between two links of the arm that share no joint, taken as "
+                             "capsules of --link-radius, where it occurs and how many samples collide; with "
+                             "--multi-start the candidates are also ranked with it, on --clearance's samples when "
+                             "that is given too (default: 0 = off)")
     parser.add_argument('--multi-start', type=_seed_count, default=0, metavar='S',
                         help="Run S seeds per problem in one launch — the straight line plus S-1 smooth random bumps — "
                              "and keep the best by (constraints fulfilled, collision-free, loss); collisions count when "
@@ -195,6 +203,8 @@ def multistart_report(info):
     pick = (lambda a: np.asarray(a)) if first else (lambda a: np.asarray(a)[0])  # noqa: E731
     winner, rank, st = int(pick(info["winner"])), pick(info["rank"]), {k: pick(v) for k, v in info["stats"].items()}
     ncol = pick(info["reports"]["n_colliding"]) if "reports" in info else None
+    if "self_reports" in info:  # --self-clearance: the ranking saw both checks' counts
+        ncol = pick(info["self_reports"]["n_colliding"]) + (0 if ncol is None else ncol)
     print("multi-start:", info["n_seeds"], "seeds, winner candidate", winner,
           "(ranked by constraints" + (", collisions" if ncol is not None else "") + ", loss)")
     for s in range(len(rank)):
@@ -292,6 +302,29 @@ def clearance_report(context, alpha, obstacles, args, obstacle_velocity=None):
         verdict = (str(int(first["n_colliding"])) + " colliding samples, the first at t=" +
                    str(t[int(first["first_colliding"])]))
     print(f"clearance ({M} samples): min", np.float32(first["min_clearance"]), where + ";", verdict)
+    return rep
+
+
+def self_clearance_report(context, alpha, args):
+    """--self-clearance M: the clearance of the links against each other on linspace(0, 1, M).  Prints problem 0's
+    line and returns the batch's report (Context.self_clearance)."""
+    M = args.self_clearance
+    t = np.linspace(0, 1, M, dtype=np.float32)
+    context.set_eval_times(t)
+    alpha = np.asarray(alpha, np.float32)
+    rep = context.self_clearance(alpha, link_radius=args.link_radius)
+    first = {k: (v if alpha.ndim == 2 else v[0]) for k, v in rep.items()}
+    if int(first["argmin_time"]) < 0:
+        where = "no link pairs"
+    else:
+        where = ("at t=" + str(t[int(first["argmin_time"])]) + " link " + str(int(first["argmin_link_a"])) + " link " +
+                 str(int(first["argmin_link_b"])))
+    if first["collision_free"]:
+        verdict = "collision-free"
+    else:
+        verdict = (str(int(first["n_colliding"])) + " colliding samples (" + str(int(first["n_crossing"])) +
+                   " crossing), the first at t=" + str(t[int(first["first_colliding"])]))
+    print(f"self-clearance ({M} samples): min", np.float32(first["min_clearance"]), where + ";", verdict)
     return rep
 
 
@@ -403,7 +436,14 @@ def run_batch(optimizer, args):
         print("clearance:", int(np.sum(np.asarray(ok, bool) & ~rep["collision_free"])), "of", int(np.sum(ok)),
               "problems that fulfil the constraints on the support grid collide")
         min_clearance = rep["min_clearance"]
-    batch_io.write_summary(batch_io.SUMMARY_BATCH, avg, mx, ok, stats, min_clearance=min_clearance)
+    if getattr(args, "self_clearance", 0) > 0:
+        rep = self_clearance_report(optimizer.context, alpha, args)
+        print("self-clearance:", int(np.sum(np.asarray(ok, bool) & ~rep["collision_free"])), "of", int(np.sum(ok)),
+              "problems that fulfil the constraints on the support grid self-collide")
+        batch_io.write_summary(batch_io.SUMMARY_BATCH, avg, mx, ok, stats, min_clearance=min_clearance,
+                               min_self_clearance=rep["min_clearance"])
+    else:
+        batch_io.write_summary(batch_io.SUMMARY_BATCH, avg, mx, ok, stats, min_clearance=min_clearance)
     if series is not None:
         lens = stats["series_len"]
         frames0 = series[0][: int(lens[0])]
@@ -494,6 +534,8 @@ def main(argv=None):
         dense_report(optimizer.context, result_alpha, env.obstacles, args.dense_check, optimizer.obstacle_velocity)
     if args.clearance > 0:
         clearance_report(optimizer.context, result_alpha, env.obstacles, args, optimizer.obstacle_velocity)
+    if args.self_clearance > 0:
+        self_clearance_report(optimizer.context, result_alpha, args)
     if args.extended_vis:
         p_np = np.array(p)
         print(p_np.shape)
